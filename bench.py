@@ -17,13 +17,17 @@ ml-NMS -> padded detections [8,2000,6] + labels + counts on the device.  With N 
 (weak scaling: BASELINE.json configs[3] = batch 64 over 8 GPUs) and the step ends with ONE RCCL all-gather of the
 padded detections.
 
-Prints ONE JSON line (rank 0).  `value` = chips/s over all ranks, inputs resident in HBM.
+Prints ONE JSON line (rank 0).  `value` = chips/s over all ranks, inputs resident in HBM; `ms_per_step` = one timed
+step.  A plain run sets up, warms up, times the K steps and prints the line; `--dump-outputs DIR` also writes what the
+last timed step returned (DIR/detections.npy, labels.npy, counts.npy as float32; the inputs are seeded, so two builds
+can be compared output for output).  Everything below is measured only with `--full`, after the timed region:
 `roofline` = the dominant hand-written kernel — the pyramid-packed AlignConv launch of the same batch, exactly as
 the step issues it — timed live with HIP events on the stream it is launched on; `roofline.traffic` comes from the
 recorded rocprofv3 PMC passes over this command (profiles/rNN_traffic.json, written by scripts/pmc_bench.sh) and is
 null + `traffic_stale` when the kernel sources changed since.  `cpu_baseline` = the same pipeline for a few chips
 on the host cores (oracle/pipeline.py: torch CPU convolutions + the oracle's AlignConv / ARF / pooling / decode +
-the reference's own CPU ml_nms_rotated when oracle/_ref is present), with the per-stage seconds as fields.
+the reference's own CPU ml_nms_rotated when oracle/_ref is present), with the per-stage seconds as fields; `ops`,
+`single_stream` and (N > 1) `per_rank` as their functions below describe.
 """
 import argparse
 import json
@@ -108,8 +112,14 @@ def parse():
     ap.add_argument("--candidates", type=int, default=5000,
                     help="(box,class) scores above 0.05 per chip the synthetic classifier is calibrated to")
     ap.add_argument("--dtype", default="f16", choices=["f16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ops", action="store_true", help="skip the `ops` object (BASELINE configs[0]/[1]/[4] as stated)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure `roofline`, `roofline_conv_tower`, `single_stream`, `ops`, "
+                         "`cpu_baseline` and (N > 1) `per_rank`; a plain run prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the detections, labels and counts of the last timed step to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline` and the CPU figures of `ops`")
+    ap.add_argument("--no-ops", action="store_true",
+                    help="with --full: skip the `ops` object (BASELINE configs[0]/[1]/[4] as stated)")
     ap.add_argument("--no-fam-cls", action="store_true",
                     help="skip the FAM classification branch (unused at inference; the reference evaluates it)")
     ap.add_argument("--graph", action="store_true", help="replay the step from a captured HIP graph")
@@ -122,7 +132,10 @@ def parse():
     ap.add_argument("--streams", type=int, default=3,
                     help="batches in flight: step i runs on HIP stream i %% S (independent batches; S > 1 lets the "
                          "latency-bound NMS tail of one batch overlap the convolutions of the next)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def calibrate_cls_bias(model, imgs, target_per_chip, logit_std=1.5):
@@ -608,6 +621,25 @@ def cpu_baseline(seed, candidates, chips=3):
     }
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, out):
+    """what the last timed step handed its caller -- (dets [B,K,6], labels [B,K], counts [B]), gathered over the ranks
+    when N > 1 -- as float32 .npy files in `path`.  Above DUMP_LIMIT_BYTES a fixed, seeded sample of the images is kept."""
+    import numpy as np
+    arrays = {name: t.detach().float().cpu().numpy() for name, t in zip(("detections", "labels", "counts"), out[:3])}
+    nb = arrays["counts"].shape[0]
+    per_image = sum(a.nbytes for a in arrays.values()) / max(nb, 1)
+    if per_image * nb > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(nb, int(DUMP_LIMIT_BYTES // per_image), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays["image_index"] = keep.astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------------------ launcher
 def pin_rank_cpus(local_rank, local_world):
     """give this rank a disjoint share of the CPUs the process may run on (N > 1: eight ranks each issue ~100 launches per
@@ -730,7 +762,7 @@ def main():
         dev = torch.device("cpu")
         args.streams, args.graph = 1, False
     else:
-        if rank == 0 and world == 1 and not (args.no_cpu_baseline and args.no_ops):
+        if args.full and rank == 0 and world == 1 and not (args.no_cpu_baseline and args.no_ops):
             import oracle
             oracle.build()          # the checker / CPU-baseline library, BEFORE anything touches the GPU (it may run make)
         assert torch.cuda.is_available(), "bench.py needs an MI355X"
@@ -828,8 +860,9 @@ def main():
             return step()
         slot[0] = turn[0] % len(streams)
         with torch.cuda.stream(streams[slot[0]]):
-            step()
+            r = step()
         turn[0] += 1
+        return r
 
     def issue_and_step_ms(fn, n):
         """(host time for n calls of fn to RETURN, no synchronisation) and (time until the GPU has finished them), per call"""
@@ -902,7 +935,7 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        runner()
+        last = runner()
     t_issued = time.perf_counter()
     sync()
     if dist_on:
@@ -910,17 +943,22 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     host_issue_ms = (t_issued - t0) / args.steps * 1e3          # the host's share: all runner() calls returned, nothing waited for
+    if gathers is not None:
+        # the last step's gathered batch (the side-stream gather may still be writing it: unpack() waits for it)
+        sync()
+        # clones: the attribution loop below gathers into its own object, but the timed slots stay untouched anyway
+        last = out = tuple(t_.clone() for t_ in gathers[(slot[0]) % nslots].unpack())
+        sync()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
     per_rank = None
     if dist_on:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+    if dist_on and args.full:
         # attribution of a scaling loss, OUTSIDE the timed region: every rank's step time without the collective
         # (same runner, same streams) and the collective alone on an otherwise idle GPU, gathered to rank 0
-        if gathers is not None:
-            sync()
-            # clones: the attribution loop below gathers into its own object, but the timed slots stay untouched anyway
-            out = tuple(t_.clone() for t_ in gathers[(slot[0]) % nslots].unpack())
         def loop_ms(fn, n):
             sync()
             t1 = time.perf_counter()
@@ -948,7 +986,7 @@ def main():
     # the latency-optimal setting beside the throughput one, measured after the timed region: one batch at a time on the
     # default stream (what a scaling run with the side-stream gather uses); eager launches, same step
     single_stream = None
-    if streams and not stub and world == 1 and not use_graph:
+    if args.full and streams and not stub and world == 1 and not use_graph:
         slot[0] = 0
         for _ in range(3):
             step()
@@ -1020,7 +1058,7 @@ def main():
         result["stub"] = True
         result["gather_equals_concatenation"] = bool(ok)
         result["data"] = "stub detector (launcher / gather rehearsal, not a measurement)"
-    if rank == 0:
+    if rank == 0 and args.full:
         if not stub:
             cap = capture_head_operands(model, imgs, max_cand)
             result["roofline"] = measure_alignconv(model, B, dtype, cap)
@@ -1034,6 +1072,7 @@ def main():
             except Exception as e:  # the baseline is a report, never a reason to lose the GPU number
                 result["cpu_baseline"] = {"value": None, "unit": "chips/s", "cores": os.cpu_count(), "kind": "port",
                                           "sample": "failed: %r" % (e,)}
+    if rank == 0:
         print(json.dumps(result), flush=True)
     if dist_on:
         dist.barrier()

@@ -34,7 +34,8 @@ def say(**kw):
 
 
 def fixture():
-    g = np.load(os.path.join(ROOT, "tests", "golden", "net_forward.npz"), allow_pickle=False)
+    from conftest import golden                 # the fixture is stored in parts
+    g = golden("net_forward.npz")
     names = [str(n) for n in g["names"]]
     shapes = [tuple(int(v) for v in str(s).split(",") if v) for s in g["shapes"]]
     dtypes = [str(d) for d in g["dtypes"]]

@@ -33,13 +33,13 @@ echo "== steady state"; bash scripts/prof_bench.sh r6final --no-ops > $O/prof_be
 bash scripts/prof_bench.sh r6final_s1 --streams 1 --no-ops > $O/prof_bench1.log 2>&1; head -3 $O/prof_bench1.log | cut -c1-160
 echo "== graph replay kernels"; bash scripts/graph_trace.sh > $O/graph_replay_kernels.txt 2>&1; echo "graph trace rc=$?"; tail -1 $O/graph_replay_kernels.txt
 echo "== ops report"; timeout -k 10 600 python scripts/bench_ops.py --which all > $O/ops_report.jsonl 2> $O/ops_report.err; echo "ops rc=$?"; wc -l $O/ops_report.jsonl
-echo "== bench"; timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; head -c 400 $O/bench.json; echo
-echo "== bench, RCCL world of one (side-stream gather)"; timeout -k 10 300 python bench.py --force-dist --streams 1 --no-cpu-baseline --no-ops 2>/dev/null | grep '^{' > $O/bench_rccl_world1.json; head -c 300 $O/bench_rccl_world1.json; echo
-timeout -k 10 300 python bench.py --no-cpu-baseline --no-ops --streams 1 --graph 2>/dev/null | grep '^{' > $O/bench_s1_graph.json; python -c "
+echo "== bench"; timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; head -c 400 $O/bench.json; echo
+echo "== bench, RCCL world of one (side-stream gather)"; timeout -k 10 300 python bench.py --full --force-dist --streams 1 --no-cpu-baseline --no-ops 2>/dev/null | grep '^{' > $O/bench_rccl_world1.json; head -c 300 $O/bench_rccl_world1.json; echo
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-ops --streams 1 --graph 2>/dev/null | grep '^{' > $O/bench_s1_graph.json; python -c "
 import json
 d=json.load(open('$O/bench_s1_graph.json')); print('graph replay, 1 stream', d['value'], d['ms_per_step'])"
 echo "== bench, 2 ranks sharing the card under gloo (rehearsal of the N > 1 code path: graph decision, per-rank CPU sets)"
-S2A_BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 2 --streams 1 --steps 10 --no-cpu-baseline --no-ops 2>/dev/null | grep '^{' > $O/bench_2rank_gloo.json; head -c 300 $O/bench_2rank_gloo.json; echo
+S2A_BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --full --gpus 2 --streams 1 --steps 10 --no-cpu-baseline --no-ops 2>/dev/null | grep '^{' > $O/bench_2rank_gloo.json; head -c 300 $O/bench_2rank_gloo.json; echo
 echo "== Winograd F(2,3) tower kernel against the direct one, same box (+ timing ablations)"
 timeout -k 10 300 python scripts/bench_wino.py 3 2>/dev/null | grep kernel > $O/wino_ab.jsonl; cat $O/wino_ab.jsonl | cut -c1-160
 echo "== half decode / NMS effect"; timeout -k 10 300 python scripts/half_nms_effect.py > $O/half_nms_effect.log 2>&1; tail -1 $O/half_nms_effect.log | cut -c1-400

@@ -56,7 +56,7 @@ def main():
                                "bytes": round((2 * fk + wk) * 1024), "dispatches": len(agg["FETCH_SIZE"]),
                                "batch": int(parts[1]), "pixels": int(parts[2]),
                                "sources": SOURCES, "source_sha16": sha16(SOURCES)}
-    rec["command"] = "rocprofv3 --kernel-trace --pmc <FETCH_SIZE | WRITE_SIZE> -- python bench.py --steps 4 --warmup 2 --no-cpu-baseline"
+    rec["command"] = "rocprofv3 --kernel-trace --pmc <FETCH_SIZE | WRITE_SIZE> -- python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline"
     rec["git_head"] = os.environ.get("S2A_GIT_HEAD")       # filled in when the record is copied into profiles/ (no .git on the GPU box)
     json.dump(rec, open(out, "w"), indent=1)
     print(json.dumps(rec))

@@ -1,5 +1,5 @@
 #!/bin/bash
-# kernel-trace + stats of the default bench command; steady-state per-kernel table via trace_steps.py
+# kernel-trace + stats of the full bench command (bench.py --full); steady-state per-kernel table via trace_steps.py
 # usage (on the GPU box): bash scripts/prof_bench.sh <tag> [bench args]
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
@@ -9,7 +9,7 @@ for a in "$@"; do case "$prev$a" in --gpus[2-9]*|--gpus=[2-9]*|--gpus1[0-9]*) ec
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o run -- python $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline "$@" > $OUT/bench.log 2>&1 || { echo "rocprof run failed"; tail -5 $OUT/bench.log; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o run -- python $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline "$@" > $OUT/bench.log 2>&1 || { echo "rocprof run failed"; tail -5 $OUT/bench.log; exit 1; }
 T=$(ls $OUT/*kernel_trace.csv $OUT/*/*kernel_trace.csv 2>/dev/null | head -1)
 S=$(ls $OUT/*kernel_stats.csv $OUT/*/*kernel_stats.csv 2>/dev/null | head -1)
 # the window of five steps ends inside the timed region: behind it come the single-stream loop of a multi-stream run (3 + 10 steps)

@@ -31,7 +31,7 @@ with open(os.path.join(P, RN + "_alignconv_pyramid_pmc.txt"), "w") as f:
     f.write(cat(os.path.join(G, "pmc_bench", "summary_k_dcn_patch.txt")))
     f.write("""
 # k_dcn_patch<NHWC, anchors> as the default bench step launches it (ONE pyramid-packed launch, 174 592 positions, f16, 256 -> 256),
-# rocprofv3 PMC passes over `python bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-ops` (scripts/pmc_bench.sh, tree %s).
+# rocprofv3 PMC passes over `python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-ops` (scripts/pmc_bench.sh, tree %s).
 # FETCH_SIZE / WRITE_SIZE in KiB; gfx950: FETCH_SIZE reads half of a wide coalesced read -> read bytes = 2 x %.0f KiB = %.1f MB,
 # WRITE_SIZE exact -> %.1f MB; traffic per launch = %.1f MB vs %.1f MB algorithmic (in + out + filter + anchors) = %.2fx
 # (rounds 1-5: 256.2 / 256.4 / 256.5 / 247.7 / 247.9 MB; round 6 did not touch this kernel)

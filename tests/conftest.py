@@ -1,3 +1,4 @@
+import glob
 import os
 import sys
 
@@ -15,7 +16,18 @@ def pytest_configure(config):
 
 
 def golden(name):
-    return np.load(os.path.join(GOLDEN, name))
+    """a fixture of tests/golden/; one larger than a committed file may be is stored as <stem>.npz + <stem>.1.npz,
+    <stem>.2.npz, ... (tests/golden/make_golden.py:save_parts): the parts are merged, and an array cut over several
+    parts is concatenated along its first axis in part order"""
+    path = os.path.join(GOLDEN, name)
+    parts = sorted(glob.glob(path[:-len(".npz")] + ".[0-9]*.npz"), key=lambda p: int(p.rsplit(".", 2)[1]))
+    if not parts:
+        return np.load(path)
+    merged = dict(np.load(path))
+    for p in parts:
+        for k, v in np.load(p).items():
+            merged[k] = np.concatenate([merged[k], v]) if k in merged else v
+    return merged
 
 
 def rand_rboxes(rng, n, span=1024.0, lo=4.0, hi=100.0):

@@ -472,6 +472,48 @@ def gen_formats():
     print("formats:", {k: v.shape for k, v in out.items()})
 
 
+def gen_compat_head():
+    """the reference's own Python imported against s2anet_amd.compat's alias modules (in place of its *_cuda
+    extensions): which alias each of its modules bound, and the ordered state_dict of its S2ANetHead(15) (names,
+    shapes, dtypes, parameter count) -- what tests/test_compat_cpu.py checks this repo's aliases and head against"""
+    import s2anet_amd.compat as compat
+    saved = {k: v for k, v in sys.modules.items() if k.split(".")[0] in ("models", "utils", "cv2", "torchvision")}
+    sys.dont_write_bytecode = True
+    try:
+        for k in list(saved):
+            del sys.modules[k]
+        mods = compat.install(force=True)
+        cv2 = types.ModuleType("cv2")
+        cv2.setNumThreads = lambda *a, **k: None
+        sys.modules.setdefault("cv2", cv2)
+        sys.modules.setdefault("torchvision", types.ModuleType("torchvision"))
+        sys.path.insert(0, REF)
+        from models.head import S2ANetHead
+        from models.dcn import DeformConv
+        from models.orn import ORConv2d
+        from utils.bbox_nms_rotated import multiclass_nms_rotated  # noqa: F401
+        head = S2ANetHead(15)
+        assert isinstance(head.align_conv.deform_conv, DeformConv) and isinstance(head.or_conv, ORConv2d)
+        by_id = {id(f): "%s.%s" % (n, fn) for n, m in mods.items() for fn, f in vars(m).items() if callable(f)}
+        by_id.update({id(m): n for n, m in mods.items()})          # a module or a function of one, bound by name
+        bound = sorted({"%s.%s=%s" % (mn, an, by_id[id(a)]) for mn, m in list(sys.modules.items())
+                        if mn.split(".")[0] in ("models", "utils") and m is not None and mn not in mods
+                        for an, a in vars(m).items() if id(a) in by_id})
+        sd = head.state_dict()
+        out = {"bound": np.array(bound), "names": np.array(list(sd)),
+               "shapes": np.array([",".join(str(v) for v in t.shape) for t in sd.values()]),
+               "dtypes": np.array([str(t.dtype).replace("torch.", "") for t in sd.values()]),
+               "param_count": np.int64(sum(p.numel() for p in head.parameters()))}
+    finally:
+        if REF in sys.path:
+            sys.path.remove(REF)
+        for k in [k for k in sys.modules if k.split(".")[0] in ("models", "utils", "cv2", "torchvision")]:
+            del sys.modules[k]
+        sys.modules.update(saved)
+    np.savez_compressed(os.path.join(OUT, "compat_head.npz"), **out)
+    print("compat_head:", len(out["bound"]), "bindings,", len(out["names"]), "state entries,", int(out["param_count"]), "parameters")
+
+
 def gen_net_forward():
     """The reference's OWN composed network run here: models.detector.S2ANet (backbone.py:283-354 -> neck.py:64-96 ->
     head.py:261-348 forward_single per level -> head.py:648-725 get_bboxes) in float32 on the CPU, batch 2 of 384 x 384
@@ -601,10 +643,42 @@ def gen_net_forward():
         out[f"det_{b}"], out[f"labels_{b}"] = det.numpy(), lab.numpy()
         print("net_forward: image", b, "detections", det.shape[0], "labels used", len(np.unique(lab.numpy())))
     # how far the NMS decisions are from the threshold (a detection flips only if an IoU crosses it)
-    np.savez_compressed(os.path.join(OUT, "net_forward.npz"), **out)
+    files = save_parts("net_forward", out)
     print("net_forward: entries", len(names), "params", sum(int(np.prod(s)) for s in shapes),
           "refine angle std", float(torch.cat([t[..., 4].reshape(-1) for t in pred[5]]).std()),
-          "file MB", os.path.getsize(os.path.join(OUT, "net_forward.npz")) / 1e6)
+          "files MB", [round(os.path.getsize(f) / 1e6, 3) for f in files])
+
+
+PART_BYTES = 900 << 10
+
+
+def save_parts(stem, out):
+    """np.savez_compressed(<stem>.npz) for a fixture of any size, every file below the 1 MiB a committed file may hold:
+    the arrays are packed in order into parts of at most PART_BYTES uncompressed, an array larger than that is cut along
+    its first axis, and parts after the first go to <stem>.1.npz, <stem>.2.npz, ... (tests/conftest.py:golden merges them)"""
+    parts, cur, used = [], {}, 0
+    for k, v in out.items():
+        v = np.asarray(v)
+        while v.ndim and used + v.nbytes > PART_BYTES and v.shape[0] > 1:
+            rows = int((PART_BYTES - used) // max(v.nbytes // v.shape[0], 1))
+            if rows <= 0 and not cur:
+                break                                    # one row alone is larger than a part: it goes whole
+            if rows > 0:
+                cur[k] = v[:rows]
+                v = v[rows:]
+            parts.append(cur)
+            cur, used = {}, 0
+        cur[k] = v
+        used += v.nbytes
+    parts.append(cur)
+    for old in os.listdir(OUT):
+        if old.startswith(stem + ".") and old[len(stem) + 1:-4].isdigit() and old.endswith(".npz"):
+            os.remove(os.path.join(OUT, old))
+    files = []
+    for i, part in enumerate(parts):
+        files.append(os.path.join(OUT, stem + (".npz" if i == 0 else ".%d.npz" % i)))
+        np.savez_compressed(files[-1], **part)
+    return files
 
 
 def torch_deform_conv(x, off, wgt, pad=1):
@@ -643,6 +717,7 @@ if __name__ == "__main__":
             globals()["gen_" + name]()
         sys.exit(0)
     rng = np.random.default_rng(SEED)
+    gen_compat_head()                      # first: the others replace the *_cuda modules by the reference's CPU builds
     gen_iou(rng)
     gen_nms(rng)
     gen_arf(rng)

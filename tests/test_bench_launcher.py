@@ -20,7 +20,7 @@ def _run(extra_env, *args):
 
 
 def test_self_launch_two_ranks_gloo():
-    r = _run({}, "--gpus", "2", "--steps", "1", "--warmup", "1")
+    r = _run({}, "--gpus", "2", "--steps", "1", "--warmup", "1", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout                       # rank 0 only
@@ -36,7 +36,7 @@ def test_self_launch_two_ranks_gloo():
 
 def test_self_launch_eight_ranks_gloo():
     """the driver's N = 8 shape (BASELINE configs[3]: batch 64 over 8 ranks), rehearsed on CPU with the stub detector"""
-    r = _run({}, "--gpus", "8", "--steps", "2", "--warmup", "1")
+    r = _run({}, "--gpus", "8", "--steps", "2", "--warmup", "1", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -44,6 +44,34 @@ def test_self_launch_eight_ranks_gloo():
     assert out["n_gpus"] == 8 and out["config"]["global_batch"] == 64 and out["stub"] is True
     assert out["gather_equals_concatenation"] is True and len(out["per_rank"]) == 8
     assert out["config"]["parallelism"].startswith("dp8")
+
+
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """without --full the line carries the headline only (no per-rank attribution after the timed region); --dump-outputs
+    writes the gathered batch of the last timed step as float32, the same from run to run"""
+    import numpy as np
+    import bench
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("dump%d" % k)
+        r = _run({}, "--gpus", "2", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d))
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and "per_rank" not in out
+        assert out["gather_equals_concatenation"] is True
+        dumps.append({n: np.load(d / (n + ".npy")) for n in ("detections", "labels", "counts")})
+    exp = [bench.StubDetector(rk, bench.BATCH_PER_GPU, "cpu") for rk in range(2)]
+    for n, attr in (("detections", "dets"), ("labels", "labels"), ("counts", "counts")):
+        a = dumps[0][n]
+        assert a.dtype == np.float32 and np.array_equal(a, dumps[1][n])
+        assert np.array_equal(a, np.concatenate([getattr(e, attr).float().numpy() for e in exp])), n
+
+
+def test_steps_must_be_positive():
+    r = _run({}, "--gpus", "1", "--steps", "0")
+    assert r.returncode != 0 and "--steps" in r.stderr
 
 
 def test_failed_rank_fails_the_launch():

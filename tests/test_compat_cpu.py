@@ -1,9 +1,6 @@
-"""CPU: the alias modules of s2anet_amd.compat carry the reference's pybind names; where the
-reference tree is present (build container) its own Python imports cleanly against them."""
+"""CPU: the alias modules of s2anet_amd.compat carry the reference's pybind names; the reference's own Python, imported
+against them in the build container, bound them and its head state (tests/golden/compat_head.npz)."""
 import inspect
-import os
-import sys
-import types
 
 import pytest
 
@@ -38,40 +35,30 @@ def test_alias_modules_have_reference_names():
     assert callable(mods["utils.ml_nms_rotated.ml_nms_rotated_cuda"].ml_nms_rotated)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/models"), reason="reference tree not present")
 def test_reference_python_imports_against_aliases():
+    """the reference's own Python, imported against the alias modules in the build container (tests/golden/compat_head.npz,
+    make_golden.py:gen_compat_head), bound these modules and functions; its S2ANetHead(15) state loads into this repo's
+    head unchanged"""
+    import torch
     import s2anet_amd.compat as compat
-    saved = {k: v for k, v in sys.modules.items() if k.split(".")[0] in ("models", "utils", "cv2", "torchvision")}
-    sys.dont_write_bytecode = True
-    try:
-        for k in list(saved):
-            del sys.modules[k]
-        compat.install(force=True)
-        cv2 = types.ModuleType("cv2")
-        cv2.setNumThreads = lambda *a, **k: None
-        sys.modules.setdefault("cv2", cv2)
-        sys.modules.setdefault("torchvision", types.ModuleType("torchvision"))
-        sys.path.insert(0, "/root/reference")
-        from models.head import S2ANetHead                       # noqa: F401  (reference code)
-        from models.dcn import DeformConv as RefDeformConv
-        from models.orn import ORConv2d as RefORConv2d
-        from utils.bbox_nms_rotated import multiclass_nms_rotated as ref_mc   # noqa: F401
-        ref_dc = sys.modules["models.dcn.deform_conv"]   # (models.dcn re-exports a function of that name)
-        assert ref_dc.deform_conv_cuda is sys.modules["models.dcn.deform_conv_cuda"]
-        head = S2ANetHead(15)
-        assert sum(p.numel() for p in head.parameters()) == 4919592
-        assert isinstance(head.align_conv.deform_conv, RefDeformConv) and isinstance(head.or_conv, RefORConv2d)
-        # the reference head's parameters load into this repo's head unchanged
-        from s2anet_amd.head import S2ANetHead as OurHead
-        ours = OurHead(15)
-        missing, unexpected = ours.load_state_dict(head.state_dict(), strict=True)
-        assert not missing and not unexpected
-    finally:
-        if "/root/reference" in sys.path:
-            sys.path.remove("/root/reference")
-        for k in [k for k in sys.modules if k.split(".")[0] in ("models", "utils", "cv2", "torchvision")]:
-            del sys.modules[k]
-        sys.modules.update(saved)
+    from conftest import golden
+    from s2anet_amd.head import S2ANetHead as OurHead
+    g = golden("compat_head.npz")
+    mods = compat.build_modules()
+    assert len(g["bound"]) >= 4
+    for b in g["bound"]:
+        user, target = str(b).split("=")
+        name = target if target in mods else target.rsplit(".", 1)[0]
+        assert name in mods, b                                          # an alias module of that name ...
+        if name != target:
+            assert callable(getattr(mods[name], target.rsplit(".", 1)[1], None)), b    # ... with that function
+    assert int(g["param_count"]) == 4919592
+    state = {str(n): torch.zeros([int(v) for v in str(s).split(",") if v], dtype=getattr(torch, str(d)))
+             for n, s, d in zip(g["names"], g["shapes"], g["dtypes"])}
+    ours = OurHead(15)
+    missing, unexpected = ours.load_state_dict(state, strict=True)
+    assert not missing and not unexpected
+    assert sum(p.numel() for p in ours.parameters()) == int(g["param_count"])
 
 
 def test_reference_checkpoint_loads_by_position(tmp_path):
