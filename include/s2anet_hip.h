@@ -233,6 +233,11 @@ int s2a_rie_backward(const uint8_t* main_direction, const void* grad_output, int
  * x[B,C,H,W] -> out[B,C/nOri,H,W] = max over each group of nOri consecutive channels. */
 int s2a_rot_inv_pool(const void* x, int64_t batch, int64_t channels, int64_t hw, int n_orientation,
                      int dtype, int layout, void* out, s2a_stream_t stream);
+/* Its backward: grad_input[B,C,H,W] (every element written) = grad_output[B,C/nOri,H,W] at the maximal orientation of
+ * each group of x (the lowest index on a tie, as torch.max(dim)), 0 elsewhere.  x, grad_output and grad_input share
+ * dtype (f32 / f16) and layout (S2A_LAYOUT_NCHW / S2A_LAYOUT_NHWC). */
+int s2a_rot_inv_pool_backward(const void* x, const void* grad_output, int64_t batch, int64_t channels, int64_t hw,
+                              int n_orientation, int dtype, int layout, void* grad_input, s2a_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Deformable convolution v1 forward.  Replaces
@@ -533,6 +538,74 @@ int64_t s2a_stem_packed_elems(void);
 int s2a_stem_pack_weight_f16(const void* weight, void* packed, s2a_stream_t stream);
 int s2a_stem_u8_f16(const void* image_u8, const void* weight_packed, const void* bias, void* out,
                     int64_t batch, int64_t height, int64_t width, float divisor, s2a_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * S2ANet training loss: compute_loss -> compute_loss_single_level of the reference (models/head.py:353-646) for BOTH
+ * modules (0 = FAM, 1 = ODM), all levels and all images in one forward call, after the assignment
+ * (s2a_assign_labels, one call per image and module).
+ *
+ *   classification  focal BCE with logits (utils/loss.py:31-58): alpha factor t*alpha + (1-t)(1-alpha), modulating
+ *                   factor (1 - p_t)^fl_gamma; positives: one-hot target on the gt's class, negatives: all-zero target,
+ *                   ignored anchors (-2): nothing, zero gradient
+ *   regression      positives only: smooth-L1 (beta = smooth_l1_beta) of the prediction against rboxes_encode(anchor, gt)
+ *                   (models/boxes.py:166-221, relative encoding), summed over the 5 components
+ *   weighting       level sums x fpn_balance; module sums / max(positives of the module over all levels and images,
+ *                   batch); regression x reg_balance; both ODM terms x odm_balance
+ *
+ * Maps are dense NCHW: cls [B,num_classes,H,W], bbox [B,5,H,W], f32 or f16 each (computed in f32).  anchors: f32,
+ * [H*W,5] shared by all images (anchor_batch_stride 0, the FAM grid anchors) or [B,H,W,5] (stride H*W*5, the ODM
+ * refined anchors).  grad_cls / grad_bbox: f32 maps of the cls / bbox shapes that receive the gradient of the
+ * UNNORMALISED, fpn_balance-weighted loss (every element written); s2a_s2anet_loss_backward scales them.
+ * Both modules of a level must have the same H, W.  At most S2A_LOSS_MAX_LEVELS levels. */
+#define S2A_LOSS_MAX_LEVELS 8
+
+typedef struct s2a_loss_map {
+  const void* cls;
+  const void* bbox;
+  const float* anchors;
+  float* grad_cls;
+  float* grad_bbox;
+  int64_t anchor_batch_stride; /* floats between two images' anchors: 0 or H*W*5 */
+  int32_t height, width;
+  int32_t cls_dtype, bbox_dtype; /* S2A_DTYPE_F32 / S2A_DTYPE_F16 */
+  float fpn_balance;
+  int32_t reserved;
+} s2a_loss_map;
+
+typedef struct s2a_loss_params {
+  int32_t batch, num_classes, n_levels, reserved;
+  float fl_gamma, fl_alpha, smooth_l1_beta, reg_balance, odm_balance;
+  s2a_loss_map map[2][S2A_LOSS_MAX_LEVELS]; /* [module][level] */
+} s2a_loss_params;
+
+/* assign_ids   int64 [2, B, A], A = sum of H*W over the levels (levels concatenated in order, row-major (y, x) within
+ *              a level): -2 ignore, -1 negative, >= 0 index of the gt within its image (s2a_assign_labels);
+ *              an index >= that image's gt count is treated as ignored
+ * targets      f32 [G,7] = (image, class, x, y, w, h, angle), px / rad, sorted by image; NULL when G == 0
+ * target_offsets int64 [B+1]: image b owns rows target_offsets[b] .. target_offsets[b+1]-1 (the gt of id k is row
+ *              target_offsets[b] + k); a class outside [0, num_classes) gives an all-zero target
+ * loss [1], items [4] (fam_cls, fam_reg, odm_cls, odm_reg) f32; norm [4] f32: the factors that turn the stored
+ *              gradients into those of loss (FAM cls, FAM reg, ODM cls, ODM reg), read by the backward
+ * Two launches, no host synchronisation, no atomics: the sums are reduced in a fixed order (bit-reproducible).
+ * workspace: s2a_s2anet_loss_workspace_bytes(B, A). */
+size_t s2a_s2anet_loss_workspace_bytes(int64_t batch, int64_t anchors_per_image);
+int s2a_s2anet_loss_forward(const s2a_loss_params* params, const int64_t* assign_ids, const float* targets,
+                            const int64_t* target_offsets, float* loss, float* items, float* norm, void* workspace,
+                            size_t workspace_bytes, s2a_stream_t stream);
+
+/* Backward of s2a_s2anet_loss_forward, one launch: dst[i] = src[i] * grad_loss[0] * norm[norm_index] for every map
+ * (src: a grad_cls / grad_bbox map of the forward, dst: the gradient of the prediction in its dtype, numel elements).
+ * norm_index: 0 FAM cls, 1 FAM bbox, 2 ODM cls, 3 ODM bbox.  grad_loss: device f32 [1] (the incoming gradient of
+ * loss, e.g. a GradScaler scale).  At most 4 * S2A_LOSS_MAX_LEVELS maps. */
+typedef struct s2a_loss_grad_map {
+  const float* src;
+  void* dst;
+  int64_t numel;
+  int32_t dtype;
+  int32_t norm_index;
+} s2a_loss_grad_map;
+int s2a_s2anet_loss_backward(const s2a_loss_grad_map* maps, int n_maps, const float* grad_loss, const float* norm,
+                             s2a_stream_t stream);
 
 /* 0 for a normal build; non-zero when an object was compiled with a measurement / ablation switch (-DS2A_MEASURE,
  * -DS2A_ABL=..., -DS2A_STAMP=1: such a build may skip work or print diagnostics). */

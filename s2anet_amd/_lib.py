@@ -41,6 +41,29 @@ class Pyramid(ctypes.Structure):
                 ("stride", c_f32 * 8)]
 
 
+LOSS_MAX_LEVELS = 8
+
+
+class LossMap(ctypes.Structure):
+    """s2a_loss_map: one (module, level) of the training loss"""
+    _fields_ = [("cls", c_vp), ("bbox", c_vp), ("anchors", c_vp), ("grad_cls", c_vp), ("grad_bbox", c_vp),
+                ("anchor_batch_stride", c_i64), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
+                ("cls_dtype", ctypes.c_int32), ("bbox_dtype", ctypes.c_int32), ("fpn_balance", c_f32),
+                ("reserved", ctypes.c_int32)]
+
+
+class LossParams(ctypes.Structure):
+    """s2a_loss_params"""
+    _fields_ = [("batch", ctypes.c_int32), ("num_classes", ctypes.c_int32), ("n_levels", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("fl_gamma", c_f32), ("fl_alpha", c_f32), ("smooth_l1_beta", c_f32),
+                ("reg_balance", c_f32), ("odm_balance", c_f32), ("map", (LossMap * LOSS_MAX_LEVELS) * 2)]
+
+
+class LossGradMap(ctypes.Structure):
+    """s2a_loss_grad_map"""
+    _fields_ = [("src", c_vp), ("dst", c_vp), ("numel", c_i64), ("dtype", ctypes.c_int32), ("norm_index", ctypes.c_int32)]
+
+
 # every symbol include/s2anet_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "s2a_last_error": (ctypes.c_char_p, []),
@@ -77,6 +100,10 @@ SYMBOLS = {
     "s2a_rie_forward": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp]),
     "s2a_rie_backward": (c_int, [c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp]),
     "s2a_rot_inv_pool": (c_int, [c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_vp]),
+    "s2a_rot_inv_pool_backward": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_vp]),
+    "s2a_s2anet_loss_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "s2a_s2anet_loss_forward": (c_int, [ctypes.POINTER(LossParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "s2a_s2anet_loss_backward": (c_int, [ctypes.POINTER(LossGradMap), c_int, c_vp, c_vp, c_vp]),
     "s2a_deform_conv_workspace_bytes": (c_sz, [ctypes.POINTER(DcnParams)]),
     "s2a_deform_conv_forward": (c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(DcnParams), c_vp,
                                         c_sz, c_vp]),

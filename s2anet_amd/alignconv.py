@@ -12,7 +12,8 @@ import torch.nn as nn
 from torch.nn.modules.utils import _pair
 
 from . import _lib
-from .dcn import DeformConv, _is_nhwc
+from .dcn import (DeformConv, _fused_backward, _fused_backward_ok, _is_nhwc, deform_conv_backward_input_cuda,
+                  deform_conv_backward_parameters_cuda)
 
 
 def align_offsets(anchors, featmap_size, stride, kernel_size=3):
@@ -66,6 +67,45 @@ def align_conv_forward(x, anchors, weight, stride, relu=True, packed=False, out_
     return out
 
 
+class AlignConvFunction(torch.autograd.Function):
+    """the fused AlignConv (align_conv_forward, ReLU included) with a backward: the sampling offsets are rebuilt with
+    align_offsets (the ones the unfused route feeds deform_conv), grad_output is masked by the saved output > 0 (the
+    fused ReLU), and the deformable-conv backward of DeformConvFunction gives the input and weight gradients.  The
+    anchors get none (they are detached in the reference, models/head.py:322)."""
+
+    @staticmethod
+    def forward(ctx, x, anchors, weight, stride):
+        out = align_conv_forward(x, anchors, weight, stride, relu=True)
+        ctx.stride = stride
+        ctx.save_for_backward(x, anchors, weight, out)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        x, anchors, weight, out = ctx.saved_tensors
+        B, C, H, W = x.shape
+        offset = align_offsets(anchors.detach().reshape(B, H * W, 5), (H, W), ctx.stride, 3)
+        go = grad_output.masked_fill(out <= 0, 0)
+        w = weight.type_as(x)
+        one = (1, 1)
+        if _fused_backward_ok(x, offset, w, go, one, one, one, 1, 1):
+            gin, _, gw = _fused_backward(x, offset, w, go)
+        else:
+            cur = min(64, B)
+            args = (3, 3, 1, 1, 1, 1, 1, 1, 1, 1)
+            gin = torch.zeros_like(x, memory_format=torch.contiguous_format)
+            deform_conv_backward_input_cuda(x, offset, go, gin, torch.zeros_like(offset), w, None, *args, cur)
+            gw = torch.zeros_like(w)
+            deform_conv_backward_parameters_cuda(x, offset, go, gw, None, None, *args, 1, cur)
+        return gin, None, gw.to(weight.dtype), None
+
+
+def align_conv(x, anchors, weight, stride):
+    """differentiable fused AlignConv (AlignConvFunction): relu(deform_conv(x, align_offsets(anchors), weight))"""
+    return AlignConvFunction.apply(x, anchors, weight, stride)
+
+
 class AlignConv(nn.Module):
     def __init__(self, in_channels, out_channels, kernel_size=3, deformable_groups=1):
         super().__init__()
@@ -104,6 +144,6 @@ class AlignConv(nn.Module):
             if not (torch.is_grad_enabled() and self.deform_conv.weight.requires_grad):
                 return align_conv_forward(x, anchors, self.packed_weight(x.dtype), stride, relu=True, packed=True,
                                           out_channels=self.deform_conv.out_channels)
-            return align_conv_forward(x, anchors, self.deform_conv.weight, stride, relu=True)
+            return align_conv(x, anchors, self.deform_conv.weight, stride)
         offset = align_offsets(anchors.reshape(num_imgs, H * W, 5), (H, W), stride, self.kernel_size[0])
         return self.relu(self.deform_conv(x, offset))

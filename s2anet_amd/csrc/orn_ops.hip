@@ -259,3 +259,60 @@ extern "C" int s2a_rot_inv_pool(const void* x, int64_t batch, int64_t channels, 
   S2A_LAUNCH_CHECK();
   return S2A_OK;
 }
+
+// ---------------------------------------------------------------- rotation-invariant pooling, backward
+// d/dx of max over each group of nOri consecutive channels: the group's gradient goes to its maximal orientation, the
+// LOWEST index on a tie (torch.max(dim) as rotation_invariant_pooling.py:19-27 uses it); every other channel gets 0.
+// One thread per (n, group, pixel); every element of grad_input is written.
+namespace s2a {
+namespace {
+template <typename T>
+__global__ void k_ripool_backward(const T* __restrict__ x, const T* __restrict__ g, int64_t batch, int64_t G, int64_t hw,
+                                  int n_ori, int nhwc, T* __restrict__ gin) {
+  const int64_t total = batch * G * hw;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t base, step, gi;
+    if (nhwc) {                       // i = (n * hw + pixel) * G + group
+      base = i * n_ori;
+      step = 1;
+      gi = i;
+    } else {                          // i = (n * G + group) * hw + pixel
+      const int64_t pix = i % hw, ng = i / hw;
+      base = ng * n_ori * hw + pix;
+      step = hw;
+      gi = i;
+    }
+    float mx = (float)x[base];
+    int d = 0;
+    for (int l = 1; l < n_ori; l++) {
+      const float v = (float)x[base + l * step];
+      if (v > mx) { mx = v; d = l; }
+    }
+    const T gv = g[gi];
+    for (int l = 0; l < n_ori; l++) gin[base + l * step] = l == d ? gv : (T)0.0f;
+  }
+}
+}  // namespace
+}  // namespace s2a
+
+extern "C" int s2a_rot_inv_pool_backward(const void* x, const void* grad_output, int64_t batch, int64_t channels, int64_t hw,
+                                         int n_orientation, int dtype, int layout, void* grad_input, s2a_stream_t stream) {
+  S2A_CHECK_ARG(batch >= 0 && channels >= 0 && hw >= 0 && n_orientation > 0, "rot_inv_pool_backward: bad shape");
+  S2A_CHECK_ARG(channels % n_orientation == 0, "rot_inv_pool_backward: channels %% nOrientation != 0");
+  S2A_CHECK_ARG(dtype == S2A_DTYPE_F32 || dtype == S2A_DTYPE_F16, "rot_inv_pool_backward: dtype");
+  S2A_CHECK_ARG(layout == S2A_LAYOUT_NCHW || layout == S2A_LAYOUT_NHWC, "rot_inv_pool_backward: layout");
+  const int64_t G = channels / n_orientation;
+  const int64_t total = batch * G * hw;
+  if (total == 0) return S2A_OK;
+  S2A_CHECK_ARG(x && grad_output && grad_input, "rot_inv_pool_backward: NULL tensor");
+  hipStream_t st = as_stream(stream);
+  const int nhwc = layout == S2A_LAYOUT_NHWC;
+  if (dtype == S2A_DTYPE_F32)
+    k_ripool_backward<float><<<grid_cap(total), 256, 0, st>>>((const float*)x, (const float*)grad_output, batch, G, hw,
+                                                              n_orientation, nhwc, (float*)grad_input);
+  else
+    k_ripool_backward<_Float16><<<grid_cap(total), 256, 0, st>>>((const _Float16*)x, (const _Float16*)grad_output, batch, G,
+                                                                 hw, n_orientation, nhwc, (_Float16*)grad_input);
+  S2A_LAUNCH_CHECK();
+  return S2A_OK;
+}

@@ -215,8 +215,11 @@ class S2ANet(nn.Module):
         self.neck = FPN(num_outs=len(self.stride))
         self.head = S2ANetHead(num_classes=num_classes, featmap_strides=self.stride, **head_kw)
 
-    def forward(self, imgs, post_process=False):
-        return self.head(self.neck(self.backbone(imgs)), post_process=post_process)
+    def forward(self, imgs, targets=None, post_process=False):
+        """models/detector.py:28-35: the head gets imgs_size = imgs.shape[-2:] (h, w) to scale targets to pixels"""
+        if isinstance(targets, bool):
+            targets, post_process = None, targets
+        return self.head(self.neck(self.backbone(imgs)), targets, imgs.shape[-2:], post_process=post_process)
 
     def features_to_pred(self, imgs, backbone_out=None, **pyramid_kw):
         """pyramid_kw: ``anchors`` / ``trace`` of S2ANetHead.forward_pyramid (pyramid-packed path only)"""

@@ -19,8 +19,9 @@ import torch.nn as nn
 
 from . import _lib
 from .alignconv import AlignConv
+from .loss import LOSS_DEFAULTS, grid_anchors, s2anet_loss
 from .orn import ORConv2d, RotationInvariantPooling
-from .rotated import batched_multiclass_nms_rotated, multiclass_nms_rotated
+from .rotated import assign_labels, batched_multiclass_nms_rotated, multiclass_nms_rotated
 
 
 def delta2bbox_rotated(rois, deltas, wh_ratio_clip=16 / 1000):
@@ -87,6 +88,12 @@ class S2ANetHead(nn.Module):
         self.max_before_nms_per_level = max_before_nms_per_level
         self.max_per_img = max_per_img
         self.compute_fam_cls = compute_fam_cls      # the reference always evaluates it (head.py:306)
+        # loss settings (head.py:82-135): plain attributes, not buffers, so that the state_dict stays the reference's
+        self.imgs_size = (1024, 1024)
+        self.fl_gamma, self.fl_alpha = LOSS_DEFAULTS["fl_gamma"], LOSS_DEFAULTS["fl_alpha"]
+        self.smoothL1_beta = LOSS_DEFAULTS["smoothL1_beta"]
+        self.FPN_balance = LOSS_DEFAULTS["FPN_balance"]
+        self.reg_balance, self.odm_balance = LOSS_DEFAULTS["reg_balance"], LOSS_DEFAULTS["odm_balance"]
         fam_reg, fam_cls, odm_reg, odm_cls = [], [], [], []
         for i in range(stacked_convs):
             cin = in_channels if i == 0 else feat_channels
@@ -214,15 +221,81 @@ class S2ANetHead(nn.Module):
                 [layout.level(odm_bbox, l, 5) for l in range(n)],
                 [layout.rows(anchors, l).view(layout.batch, *layout.sizes[l], 5) for l in range(n)])
 
-    def forward(self, feats, post_process=False):
+    def forward(self, feats, targets=None, imgs_size=None, post_process=False):
+        """head.py:261-293.  targets[N,7] = (image, class, x, y, w, h, angle) with x, y, w, h normalised: scaled to
+        pixels IN PLACE by imgs_size (h, w) as the reference does, then compute_loss fills "loss" / "loss_items".
+        A bool in the second place is post_process (the earlier forward(feats, post_process) form)."""
+        if isinstance(targets, bool):
+            targets, post_process = None, targets
         per_level = [self.forward_single(f, s) for f, s in zip(feats, self.featmap_strides)]
         p = tuple(map(list, zip(*per_level)))
         results = {"loss": None, "loss_items": None, "boxes_ls": None, "pred": None}
+        if targets is not None:
+            if imgs_size is None:
+                raise ValueError("forward(feats, targets) needs imgs_size to scale the targets to pixels")
+            self.imgs_size = tuple(int(v) for v in imgs_size)
+            targets[:, [2, 4]] = targets[:, [2, 4]] * imgs_size[1]
+            targets[:, [3, 5]] = targets[:, [3, 5]] * imgs_size[0]
+            results["loss"], results["loss_items"] = self.compute_loss(p, targets)
         if post_process:
             results["boxes_ls"] = self.get_bboxes(p)
-        else:
+        if targets is None and not post_process:
             results["pred"] = p
         return results
+
+    # ------------------------------------------------------------------ loss (head.py:353-646)
+    def init_grid_anchors(self, featmap_sizes, device):
+        """the reference's p[4]: per-level grid anchors [H*W,5] f32 (models/anchors.py:75-126)"""
+        return [grid_anchors(hw, s, self.anchor_scale, device) for hw, s in zip(featmap_sizes, self.featmap_strides)]
+
+    def _loss_pred(self, p):
+        """this library's 5-list p (refined anchors at p[4]) or the reference's 6-list (grid anchors at p[4], refined
+        anchors at p[5]) -> the 6-list"""
+        p = list(p)
+        if len(p) == 5:
+            sizes = [tuple(b.shape[2:]) for b in p[1]]
+            p = p[:4] + [self.init_grid_anchors(sizes, p[1][0].device), p[4]]
+        if len(p) != 6:
+            raise ValueError(f"p must be the 5 per-level lists of forward() or the reference's 6, got {len(p)}")
+        if any(t is None for t in p[0]):
+            raise ValueError("compute_loss needs the FAM classification: this head was built with compute_fam_cls=False")
+        return p
+
+    def assign_labels_fam_odm(self, p, targets):
+        """head.py:439-537 for the whole batch: -> (assign_ids int64 [2,B,A] (FAM, ODM; levels concatenated per image),
+        targets sorted by image [N,7] f32, row offsets int64 [B+1]).  One host synchronisation (the per-image target
+        counts), then 2*B assign_labels calls."""
+        p = self._loss_pred(p)
+        B = p[1][0].shape[0]
+        dev = p[1][0].device
+        init_all = torch.cat([a.reshape(-1, 5) for a in p[4]], 0).float()
+        refine_all = torch.cat([a.reshape(B, -1, 5) for a in p[5]], 1).detach().float()
+        t = targets.detach().float().reshape(-1, 7)
+        img = t[:, 0].long()
+        order = torch.argsort(img, stable=True)
+        ts = t[order]
+        counts_dev = torch.bincount(img, minlength=B)[:B]
+        offsets = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+        offsets[1:] = torch.cumsum(counts_dev, 0)
+        counts = counts_dev.tolist()                       # the one host sync of the assignment
+        fam, odm, start = [], [], 0
+        for b in range(B):
+            gt = ts[start:start + counts[b], 2:7]
+            start += counts[b]
+            fam.append(assign_labels(init_all, gt, imgs_size=self.imgs_size))
+            odm.append(assign_labels(refine_all[b], gt, imgs_size=self.imgs_size))
+        return torch.stack([torch.stack(fam), torch.stack(odm)]), ts, offsets
+
+    def compute_loss(self, p, targets):
+        """head.py:353-436: p = forward()'s 5 lists or the reference's 6; targets[N,7] (image, class, x, y, w, h,
+        angle) in pixels / rad -> (loss [1] f32, loss_items float32 numpy [4] = fam_cls, fam_reg, odm_cls, odm_reg).
+        Host syncs: the target counts of the assignment and the loss_items read-back."""
+        p = self._loss_pred(p)
+        ids, ts, offsets = self.assign_labels_fam_odm(p, targets)
+        loss, items = s2anet_loss(p[0], p[1], p[2], p[3], p[4], p[5], ids, ts, offsets, fl_gamma=self.fl_gamma,
+                                  fl_alpha=self.fl_alpha, smoothL1_beta=self.smoothL1_beta, FPN_balance=self.FPN_balance,
+                                  reg_balance=self.reg_balance, odm_balance=self.odm_balance)
+        return loss, items.detach().cpu().numpy()
 
     # ------------------------------------------------------------------ decode + NMS, batched
     def candidates(self, p, raw_logits=False):

@@ -229,6 +229,19 @@ class ORConv2d(nn.Conv2d):
 
 
 def rot_inv_pool(x, n_orientation=8):
+    """RotationInvariantPooling (rotation_invariant_pooling.py:19-27): max over each group of n_orientation channels;
+    differentiable (RotInvPoolFunction) when grad is enabled and x requires grad, the same kernel either way"""
+    if torch.is_grad_enabled() and x.requires_grad:
+        return RotInvPoolFunction.apply(x, n_orientation)
+    return _rot_inv_pool_forward(x, n_orientation)
+
+
+def _ripool_layout(x):
+    nhwc = x.dim() == 4 and not x.is_contiguous() and x.is_contiguous(memory_format=torch.channels_last)
+    return nhwc, (x if nhwc else x.contiguous())
+
+
+def _rot_inv_pool_forward(x, n_orientation):
     _lib.require_cuda(x)
     N, c, h, w = x.shape
     if c % n_orientation:
@@ -243,6 +256,39 @@ def rot_inv_pool(x, n_orientation=8):
             _lib.ptr(x), N, c, h * w, n_orientation, _lib.dtype_code(x),
             _lib.LAYOUT_NHWC if nhwc else _lib.LAYOUT_NCHW, _lib.ptr(out), _lib.stream_ptr(x.device)))
     return out
+
+
+def rot_inv_pool_backward(x, grad_output, n_orientation=8):
+    """grad_input of rot_inv_pool: grad_output at the maximal orientation of each group (lowest index on a tie, as
+    torch.max(dim)), 0 elsewhere; in x's layout (NCHW or channels_last) and dtype"""
+    _lib.require_cuda(x, grad_output)
+    N, c, h, w = x.shape
+    if c % n_orientation:
+        raise RuntimeError("channels must be a multiple of nOrientation")
+    nhwc, x = _ripool_layout(x)
+    fmt = torch.channels_last if nhwc else torch.contiguous_format
+    g = grad_output.to(x.dtype).contiguous(memory_format=fmt)
+    assert g.shape == (N, c // n_orientation, h, w)
+    gin = torch.empty((N, c, h, w), dtype=x.dtype, device=x.device, memory_format=fmt)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().s2a_rot_inv_pool_backward(
+            _lib.ptr(x), _lib.ptr(g), N, c, h * w, n_orientation, _lib.dtype_code(x),
+            _lib.LAYOUT_NHWC if nhwc else _lib.LAYOUT_NCHW, _lib.ptr(gin), _lib.stream_ptr(x.device)))
+    return gin
+
+
+class RotInvPoolFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, n_orientation):
+        ctx.n_orientation = n_orientation
+        ctx.save_for_backward(x)
+        return _rot_inv_pool_forward(x, n_orientation)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        (x,) = ctx.saved_tensors
+        return rot_inv_pool_backward(x, grad_output, ctx.n_orientation), None
 
 
 class RotationInvariantPooling(nn.Module):
