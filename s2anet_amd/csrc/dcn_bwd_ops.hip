@@ -416,7 +416,7 @@ __global__ __launch_bounds__(kBThreads) void k_dcn_bwd_input(const _Float16* __r
   float* s_G = reinterpret_cast<float*>(s_go + kBPos * kBGoRow);            // [9][64][kBGRow] f32: column gradient of a chunk
   char* s_patch = reinterpret_cast<char*>(s_G + 9 * kBPos * kBGRow);        // [288][32 halfs]
   BTap* s_tab = reinterpret_cast<BTap*>(s_patch + kIPix * kBCh * 2);        // [64 * 9]
-  _Float16* s_frac = reinterpret_cast<_Float16*>(s_tab + kBPos * 9);        // [64 * 9][2]: lh, lw
+  _Float16* s_frac = reinterpret_cast<_Float16*>(s_tab + kBPos * 9);        // [64 * 9][2]: lh, lw as the signed distance to the nearer corner
   float* s_goff = reinterpret_cast<float*>(s_frac + kBPos * 9 * 2);         // [64 * 9][2]
   unsigned* s_list = reinterpret_cast<unsigned*>(s_goff + kBPos * 9 * 2);   // [64 * 9 * 4]: (tap * 64 + pos) << 16 | weight (f16 bits)
   unsigned* s_start = s_list + kBPos * 9 * 4;                               // [288 + 1] first list entry of a window pixel
@@ -471,8 +471,11 @@ __global__ __launch_bounds__(kBThreads) void k_dcn_bwd_input(const _Float16* __r
       }
     }
     s_tab[e] = tp;
-    s_frac[2 * e] = (_Float16)lh;
-    s_frac[2 * e + 1] = (_Float16)lw;
+    // (kept as lh or lh - 1, whichever is nearer 0, both exact in f32: f16 holds small magnitudes to u16 RELATIVE, so hh = 1 - lh
+    // keeps its precision as well when lh is close to 1.  Stored as lh itself, lh = 1 - 2^-12 rounded to 1 and hh to 0: a sample
+    // in the band (H-1, H) or (W-1, W), whose far corners lie outside the image, lost its whole offset gradient.)
+    s_frac[2 * e] = (_Float16)(lh <= 0.5f ? lh : lh - 1.f);
+    s_frac[2 * e + 1] = (_Float16)(lw <= 0.5f ? lw : lw - 1.f);
   }
   __syncthreads();
   // ---- the scatter of deformable_col2im turned into a GATHER: which (position, tap, corner) lands on which window pixel
@@ -636,9 +639,11 @@ __global__ __launch_bounds__(kBThreads) void k_dcn_bwd_input(const _Float16* __r
         for (int j = 0; j < 8; j++) a = __builtin_fmaf(G[j], (float)c4[k][j], a);
         d[k] = a;
       }
-      const float lh = (float)s_frac[2 * (pos * 9 + t)], lw = (float)s_frac[2 * (pos * 9 + t) + 1];
-      float gh = (1.f - lw) * (d[2] - d[0]) + lw * (d[3] - d[1]);
-      float gw = (1.f - lh) * (d[1] - d[0]) + lh * (d[3] - d[2]);
+      const float fh = (float)s_frac[2 * (pos * 9 + t)], fw = (float)s_frac[2 * (pos * 9 + t) + 1];
+      const float lh = fh < 0.f ? 1.f + fh : fh, hh = fh < 0.f ? -fh : 1.f - fh;
+      const float lw = fw < 0.f ? 1.f + fw : fw, hw = fw < 0.f ? -fw : 1.f - fw;
+      float gh = hw * (d[2] - d[0]) + lw * (d[3] - d[1]);
+      float gw = hh * (d[1] - d[0]) + lh * (d[3] - d[2]);
       gh += __shfl_xor(gh, 1); gw += __shfl_xor(gw, 1);
       gh += __shfl_xor(gh, 2); gw += __shfl_xor(gw, 2);
       if (q == 0) {                              // one owner per (position, tap): plain read-modify-write
@@ -2226,6 +2231,10 @@ int fused_bwd_run(const FusedBwdArgs& a, void* workspace, size_t workspace_bytes
   if (B == 0 || (!want_input && !want_weight)) return S2A_OK;
   S2A_CHECK_ARG(a.input && a.offset && a.grad_output, "%s: NULL tensor", who);
   S2A_CHECK_ARG(!want_input || (a.weight && a.grad_offset), "%s: NULL tensor", who);
+  // (the workspace is carved into 16-byte vector buffers; a typed f32 gradInput is cleared with 16-byte stores, k_bwd_zero4)
+  S2A_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
+  S2A_CHECK_ARG(kHalf || !want_input || !a.grad_input_typed || (reinterpret_cast<uintptr_t>(a.grad_input) & 15) == 0,
+                "%s: a float32 grad_input must be 16-byte aligned", who);
   S2A_CHECK_ARG(workspace_bytes >= fused_bwd_workspace(a.dtype, want_input, want_weight, B, C, H, W, O), "%s: workspace too small", who);
   Carver cv(workspace, workspace_bytes);
   const int64_t HW = H * W;

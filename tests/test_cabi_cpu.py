@@ -107,3 +107,33 @@ def test_argument_checks_return_codes_without_touching_the_gpu():
     assert rc == -1 and "smaller than kernel" in msg()          # deform_conv_cuda.cpp:100-103 (shape_check)
     # IoU workspace
     assert L.s2a_box_iou_rotated_workspace_bytes(10, 10) > 0
+
+
+def test_fused_backward_refuses_misaligned_buffers_without_touching_the_gpu():
+    """s2a_deform_conv_backward_typed clears a float32 grad_input with 16-byte stores and carves 16-byte vector buffers
+    out of the workspace: either pointer off a 16-byte boundary is refused with S2A_EINVAL before the first launch"""
+    import ctypes
+    from s2anet_amd import _lib
+    L = _lib.lib()
+    z = ctypes.c_void_p(0)
+    one = ctypes.c_void_p(1 << 20)     # never dereferenced: the checks fail first
+    odd4 = ctypes.c_void_p((1 << 20) + 4)
+    odd8 = ctypes.c_void_p((1 << 20) + 8)
+    B, C, H, W, O = 2, 64, 8, 8, 32
+    big = 1 << 40                      # no size check in the way: only the alignment can refuse these
+
+    def typed(dt, gin, ws, ws_bytes=big):
+        return L.s2a_deform_conv_backward_typed(dt, one, one, one, one, gin, one, one, 1.0, B, C, H, W, O, ws, ws_bytes, z)
+
+    def msg():
+        return L.s2a_last_error().decode()
+    for bad in (odd4, odd8):
+        assert typed(_lib.DTYPE_F32, bad, one) == _lib.EINVAL and "aligned" in msg() and "grad_input" in msg()
+        for dt in (_lib.DTYPE_F32, _lib.DTYPE_F16):
+            assert typed(dt, one, bad) == _lib.EINVAL and "aligned" in msg() and "workspace" in msg()
+    # controls, refused for their size before any launch: a float16 grad_input only needs its element alignment, and the
+    # accumulating entry (scalar atomics into a float32 grad_input) none beyond 4 bytes
+    assert typed(_lib.DTYPE_F16, odd8, one, 0) == _lib.EINVAL and "too small" in msg()
+    assert typed(_lib.DTYPE_F32, one, one, 0) == _lib.EINVAL and "too small" in msg()
+    rc = L.s2a_deform_conv_backward(_lib.DTYPE_F32, one, one, one, one, odd4, one, one, 1.0, B, C, H, W, O, one, 0, z)
+    assert rc == _lib.EINVAL and "too small" in msg()
