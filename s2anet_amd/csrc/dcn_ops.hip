@@ -2955,10 +2955,15 @@ static int conv3x3_pyramid_impl(const void* x, const void* weight_frag, const vo
   S2A_CHECK_ARG((channels % 64 == 0 || channels == 32) && out_channels % 64 == 0,
                 "conv_pyramid: channels must be 32 or a multiple of 64, out_channels a multiple of 64");
   LevelTab lt; int64_t pix = 0;
+  int og = out_channels % 256 == 0 ? 4 : (out_channels % 128 == 0 ? 2 : 1);
+  // A/B switch for measurements; not for the fused 1x1 head, which needs the whole channel range in one workgroup (OG = 4)
+  const char* og_env = getenv("S2A_CONV_OG");
+  if (og_env && !ex.head_w) og = std::min(og, std::max(1, atoi(og_env)));
   // Full-width towers: 16 x 16 tiles on 512-thread workgroups with the filter staged once per workgroup through
-  // LDS (ConvCfg::kWLds) -- 4-7 % faster than two 8 x 16 workgroups per CU, bit-identical.  S2A_CONV_PH=1|2: A/B switch
-  int ph = (out_channels % 256 == 0 && channels % 64 == 0) ? 2 : 1;
-  if (const char* f = getenv("S2A_CONV_PH")) ph = atoi(f) == 2 && out_channels % 256 == 0 && channels % 64 == 0 ? 2 : 1;
+  // LDS (ConvCfg::kWLds) -- 4-7 % faster than two 8 x 16 workgroups per CU, bit-identical.  S2A_CONV_PH=1|2: A/B switch.
+  // Only the OG = 4 form has 16-row tiles: the level table must be built for the tile height that is launched.
+  int ph = (og == 4 && channels % 64 == 0) ? 2 : 1;
+  if (const char* f = getenv("S2A_CONV_PH")) ph = atoi(f) == 2 && og == 4 && channels % 64 == 0 ? 2 : 1;
   const int64_t tiles = build_levels(pyr, batch, &lt, &pix, 8 * ph);
   S2A_CHECK_ARG(tiles >= 0, "conv_pyramid: bad level table (1..8 levels, positive sizes)");
   S2A_CHECK_ARG((uint64_t)pix * channels * 2 < (1ull << 31), "conv_pyramid: input too large for 32-bit offsets");
@@ -2968,8 +2973,6 @@ static int conv3x3_pyramid_impl(const void* x, const void* weight_frag, const vo
                 ((uintptr_t)bias % 8) == 0 && ((uintptr_t)residual % 16) == 0, "conv_pyramid: tensors must be 16-byte aligned");
   if (lt.n == 1) lt.n = 2, lt.tile0[1] = 0x7fffffff;   // keep the rebind path (n > 1) for a one-level table
   hipStream_t st = as_stream(stream);
-  int og = out_channels % 256 == 0 ? 4 : (out_channels % 128 == 0 ? 2 : 1);
-  if (const char* f = getenv("S2A_CONV_OG")) og = std::min(og, std::max(1, atoi(f)));   // A/B switch for measurements
   const _Float16 *X = (const _Float16*)x, *Wf = (const _Float16*)weight_frag, *Bi = (const _Float16*)bias,
                  *R = (const _Float16*)residual;
   _Float16* Y = (_Float16*)out;
