@@ -12,11 +12,12 @@ from .dcn import DeformConv, DeformConvFunction, deform_conv, deform_conv_forwar
 from .alignconv import AlignConv, AlignConvFunction, align_conv
 from .orn import RotInvPoolFunction, rot_inv_pool, rot_inv_pool_backward
 from .loss import S2ANetLossFunction, s2anet_loss, grid_anchors
+from .fused import drop_weight_caches
 
 __all__ = [
     "box_iou_rotated", "nms_rotated", "ml_nms_rotated", "multiclass_nms_rotated",
     "batched_multiclass_nms_rotated", "arf_forward", "arf_backward", "active_rotating_filter", "ORConv2d",
     "RotationInvariantPooling", "DeformConv", "DeformConvFunction", "deform_conv",
     "deform_conv_forward_cuda", "AlignConv", "AlignConvFunction", "align_conv", "RotInvPoolFunction", "rot_inv_pool",
-    "rot_inv_pool_backward", "S2ANetLossFunction", "s2anet_loss", "grid_anchors",
+    "rot_inv_pool_backward", "S2ANetLossFunction", "s2anet_loss", "grid_anchors", "drop_weight_caches",
 ]

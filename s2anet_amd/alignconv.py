@@ -117,12 +117,14 @@ class AlignConv(nn.Module):
         self._packed = None
 
     def packed_weight(self, dtype):
-        """inference-time cache of the packed filter (invalidated when the parameter changes)"""
+        """inference-time cache of the packed filter, keyed on the parameter (the rule of fused.PackedWeightCache;
+        `.data` in-place writes need s2anet_amd.drop_weight_caches)"""
         w = self.deform_conv.weight
-        key = (w._version, w.data_ptr(), dtype, w.device)
-        if self._packed is None or self._packed[0] != key:
-            self._packed = (key, pack_weight(w, dtype))
-        return self._packed[1]
+        key = (w._version, w.data_ptr(), dtype)
+        c = self._packed
+        if c is None or c[0] is not w or c[1] != key:
+            self._packed = c = (w, key, pack_weight(w, dtype), w.detach())   # the alias keeps the keyed address alive
+        return c[2]
 
     def init_weights(self):
         nn.init.normal_(self.deform_conv.weight, 0, 0.01)   # alignconv.py:25-26

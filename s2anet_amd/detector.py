@@ -141,11 +141,12 @@ class DetectorBackbone(nn.Module):
         """forward() on the raw uint8 batch with the fused stem (s2a_stem_u8_f16)"""
         from .fused import PackedWeightCache, stem_pack_weight, stem_u8
         conv = self.backbone[0][0]
-        w = conv.weight
-        key = (w._version, w.data_ptr(), w.device)
-        if getattr(self, "_stem_key", None) != key:
-            self._stem_key, self._stem_w = key, stem_pack_weight(w)
-            self._stem_b = None if conv.bias is None else conv.bias.detach().to(torch.float16).contiguous()
+        c = self.__dict__.get("_stem_cache")
+        if c is None:
+            self._stem_cache = c = PackedWeightCache()
+        # filter and bias each under their own key: a bias-only update is followed too
+        self._stem_w = c.lookup("stem", conv.weight, None, stem_pack_weight, conv.weight)
+        self._stem_b = c.get_bias(conv.bias, conv.out_channels)
         return self._stages(stem_u8(imgs_u8, self._stem_w, self._stem_b, divisor))
 
 

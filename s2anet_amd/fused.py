@@ -194,37 +194,77 @@ def conv1x1_add_up2(x, packed_weight, bias, coarse, out_channels):
 
 
 class PackedWeightCache:
-    """inference-time cache of a conv_pack_weight() result, invalidated when the tensor changes"""
+    """inference-time cache of the packed forms of ONE weight / bias pair: the fragment-order filter (conv_pack_weight),
+    the Winograd-transformed filter (conv_wino_pack_weight), the padded f16 bias, or any other packed form through
+    lookup().
+
+    Invariant: a key may contain data_ptr() only of a tensor whose storage the cache itself keeps alive, and a cache
+    entry is keyed on the *parameter* it derives from, never on an intermediate.  Every entry therefore holds the keyed
+    tensor itself plus a detach() alias of it, and hits only for that very tensor object at its recorded version and
+    address: the allocator cannot hand the address to other data while the entry lives, and a second tensor object at
+    the same address (a fresh temporary, a replaced parameter) misses.  The one intermediate that is handed in,
+    ORConv2d's ARF expansion, is itself an entry of ORConv2d.rotate_arf keyed on the 5-D parameter, with or without
+    train().
+
+    What a key follows: no_grad in-place ops, optimizer steps, load_state_dict, nn.init.*, `mod.weight = Parameter(..)`,
+    `p.data = new`, .float() / .half() / .to().  What NO key can follow: in-place writes through `.data`
+    (`p.data.copy_()`, `p.data.normal_()`, `p.data.fill_()`) - they neither bump the version counter nor move the
+    storage.  After such a write call drop_weight_caches(module)."""
 
     def __init__(self):
-        self.key, self.val = None, None
-        self.bkey, self.bval = None, None
-        self.wkey, self.wval = None, None
+        self.slots = {}
+
+    def clear(self):
+        self.slots = {}
+
+    def lookup(self, slot, t, extra, make, *args):
+        """the entry of `slot` if it was made from this very tensor in its current state, else make(*args) -> stored.
+        An entry is (tensor, version, address, extra, value, detach() alias): the alias keeps the storage alive, so that
+        the same object at the same address and version is the same memory, dtype and device included."""
+        e = self.slots.get(slot)
+        if e is not None and e[0] is t and e[1] == t._version and e[2] == t.data_ptr() and e[3] == extra:
+            return e[4]
+        e = (t, t._version, t.data_ptr(), extra, make(*args), t.detach())
+        self.slots[slot] = e
+        return e[4]
 
     def get_wino(self, w):
         """the Winograd-transformed filter (conv_wino_pack_weight) of a [O,C,3,3] weight"""
-        key = (w._version, w.data_ptr(), w.device)
-        if self.wkey != key:
-            self.wkey, self.wval = key, conv_wino_pack_weight(w)
-        return self.wval
+        return self.lookup("wino", w, None, conv_wino_pack_weight, w)
 
     def get(self, w):
-        key = (w._version, w.data_ptr(), w.device)
-        if self.key != key:
-            self.key, self.val = key, conv_pack_weight(w)
-        return self.val
+        return self.lookup("direct", w, None, conv_pack_weight, w)
 
     def get_bias(self, b, width):
         """f16 bias zero-padded to the physical channel count"""
         if b is None:
             return None
-        key = (b._version, b.data_ptr(), b.device, width)
-        if self.bkey != key:
-            v = b.detach().to(torch.float16)
-            if v.numel() < width:
-                v = torch.cat([v, v.new_zeros(width - v.numel())])
-            self.bkey, self.bval = key, v.contiguous()
-        return self.bval
+        return self.lookup("bias", b, width, _pad_bias_f16, b, width)
+
+
+def _pad_bias_f16(b, width):
+    v = b.detach().to(torch.float16)
+    if v.numel() < width:
+        v = torch.cat([v, v.new_zeros(width - v.numel())])
+    return v.contiguous()
+
+
+def drop_weight_caches(module):
+    """forget every packed / expanded weight cached in the module tree (FusedConv2d and ORConv2d packed filters and
+    biases, ORConv2d's ARF expansion, AlignConv's stage-major filter, the fused stem's filter and bias); the next
+    no-grad forward packs again from the current parameters.  Needed after in-place writes through `.data`
+    (`p.data.copy_()`, `p.data.normal_()`, ...), which no cache key can see; every other update route is followed
+    without it.  A HIP graph captured before this call replays the dropped buffers: capture it again."""
+    for m in module.modules():
+        for name in ("_packed", "_stem_cache"):
+            c = m.__dict__.get(name)
+            if isinstance(c, PackedWeightCache):
+                c.clear()
+            elif c is not None:
+                m.__dict__[name] = None
+        if m.__dict__.get("_arf_cache") is not None:
+            m._arf_cache = None
+    return module
 
 
 class FusedConv2d(nn.Conv2d):

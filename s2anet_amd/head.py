@@ -191,20 +191,18 @@ class S2ANetHead(nn.Module):
         if getattr(self, "capture", None) is not None:      # bench.py: the operands of this step's launches
             self.capture.update(layout=layout, x=x, anchors=anchors)
         al = P.align_conv(layout, x, anchors, self.align_conv.packed_weight(torch.float16), self.feat_channels)
-        wa = self.or_conv.rotate_arf()
-        if not hasattr(self.or_conv, "_packed"):
-            from .fused import PackedWeightCache
-            self.or_conv._packed = PackedWeightCache()
+        wa = self.or_conv.rotate_arf()      # the cached expansion (keyed on the 5-D parameter), in train() mode as well
+        orc = self.or_conv.packed_cache()
         if self.or_pool.nOrientation == 8 and wa.shape[0] % 64 == 0 and wino and wa.shape[1] % 32 == 0:
-            or_feat, pooled = P.conv3x3_wino(layout, al, self.or_conv._packed.get_wino(wa),
-                                             self.or_conv._packed.get_bias(self.or_conv.bias, wa.shape[0]), wa.shape[0],
+            or_feat, pooled = P.conv3x3_wino(layout, al, orc.get_wino(wa),
+                                             orc.get_bias(self.or_conv.bias, wa.shape[0]), wa.shape[0],
                                              relu=False, pool=True)
         elif self.or_pool.nOrientation == 8 and wa.shape[0] % 64 == 0:                      # conv + orientation max, one launch
-            or_feat, pooled = P.orconv_pool(layout, al, self.or_conv._packed.get(wa),
-                                            self.or_conv._packed.get_bias(self.or_conv.bias, wa.shape[0]), wa.shape[0])
+            or_feat, pooled = P.orconv_pool(layout, al, orc.get(wa),
+                                            orc.get_bias(self.or_conv.bias, wa.shape[0]), wa.shape[0])
         else:
-            or_feat = P.conv3x3(layout, al, self.or_conv._packed.get(wa),
-                                self.or_conv._packed.get_bias(self.or_conv.bias, wa.shape[0]), wa.shape[0], relu=False)
+            or_feat = P.conv3x3(layout, al, orc.get(wa),
+                                orc.get_bias(self.or_conv.bias, wa.shape[0]), wa.shape[0], relu=False)
             pooled = P.rot_inv_pool(or_feat, self.or_pool.nOrientation)                     # [P,32]
         w, b, o = self.odm_cls_head.packed_args()
         odm_cls = P.conv3x3(layout, tower(self.odm_cls_ls, pooled), w, b, o, relu=False)    # [P,64], C used

@@ -162,8 +162,13 @@ class ORConv2d(nn.Conv2d):
 
     At inference the expanded filter depends on the parameters only, so it is computed once
     and cached (the reference recomputes it on every forward of every FPN level,
-    ORConv.py:80-82); the cache is invalidated whenever the weight tensor changes
-    (version counter / dtype / device)."""
+    ORConv.py:80-82).  The cached expansion and its packed forms are used whenever no gradient is
+    asked for, in eval() and in train() mode alike, and are keyed on the 5-D parameter (object,
+    version counter, address; fused.PackedWeightCache states the rule): they follow
+    in-place updates under no_grad, optimizer steps, load_state_dict, a replaced parameter and
+    .half() / .float().  In-place writes through ``weight.data`` (``.data.normal_()``,
+    ``.data.copy_()``) are invisible to any key: call ``s2anet_amd.drop_weight_caches(module)``
+    after them."""
 
     def __init__(self, in_channels, out_channels, kernel_size=3, arf_config=None, stride=1,
                  padding=0, dilation=1, groups=1, bias=True):
@@ -202,25 +207,32 @@ class ORConv2d(nn.Conv2d):
 
     def rotate_arf(self):
         w = self.weight
-        key = (w._version, w.dtype, w.device, w.data_ptr())
-        if self.training or torch.is_grad_enabled() and w.requires_grad:
+        if torch.is_grad_enabled() and w.requires_grad:
             return active_rotating_filter(w, self.indices)
-        if self._arf_cache is None or self._arf_cache[0] != key:
+        key = (w._version, w.data_ptr(), bool(getattr(self, "channels_last", False)))
+        c = self._arf_cache
+        if c is None or c[0] is not w or c[1] != key:
             e = arf_forward(w.detach(), self.indices)
-            if getattr(self, "channels_last", False):
+            if key[2]:
                 e = e.contiguous(memory_format=torch.channels_last)
-            self._arf_cache = (key, e)
-        return self._arf_cache[1]
+            self._arf_cache = c = (w, key, e, w.detach())       # the alias keeps the keyed address from being reissued
+        return c[2]
+
+    def packed_cache(self):
+        """fused.PackedWeightCache of the cached expansion's packed forms (direct, Winograd) and the f16 bias"""
+        c = self.__dict__.get("_packed")
+        if c is None:
+            from .fused import PackedWeightCache
+            self._packed = c = PackedWeightCache()
+        return c
 
     def forward(self, input):
         w = self.rotate_arf()
         if input.is_cuda and not torch.is_grad_enabled():
-            from .fused import own_conv_ok, conv_f16, PackedWeightCache
+            from .fused import own_conv_ok, conv_f16
             if own_conv_ok(input, w.shape[1], w.shape[0], w.shape[2:], self.stride, self.padding, self.dilation,
                            self.groups):
-                if not hasattr(self, "_packed"):
-                    self._packed = PackedWeightCache()
-                return conv_f16(input, self._packed.get(w), self.bias, w.shape[0], w.shape[2], 1, False)
+                return conv_f16(input, self.packed_cache().get(w), self.bias, w.shape[0], w.shape[2], 1, False)
         if input.is_cuda and self.bias is not None and not torch.is_grad_enabled():
             from .fused import bias_act_
             y = F.conv2d(input, w, None, self.stride, self.padding, self.dilation, self.groups)
