@@ -345,6 +345,38 @@ int s2a_fam_refine_anchors(const void* bbox_pred, int64_t batch, int64_t height,
                            float stride, float anchor_scale, int dtype, int layout, float* refined,
                            s2a_stream_t stream);
 
+/* ---- whole-scene detection: chips out of a device-resident scene, merged detections back (scene_ops.hip) ----
+ *
+ * Chip gather: replaces SplitSingle / saveimagepatches (DOTA_devkit/SplitOnlyImage_multi_process.py:39-49, :68-85).
+ * scene uint8 [height,width,3] (HWC); origins int32 [n_chips,2] (left, up) on the device, any order, may reach past
+ * the scene; chips uint8 [n_chips,subsize,subsize,3].  Pixels outside the scene are 0 (the np.zeros padding, :45-46).
+ * One launch for all chips.  subsize % 16 == 0, chips 16-byte aligned, scene 4-byte aligned. */
+int s2a_scene_gather_u8(const uint8_t* scene, int64_t height, int64_t width, const int32_t* origins, int64_t n_chips,
+                        int32_t subsize, uint8_t* chips, s2a_stream_t stream);
+
+/* Scene merge: replaces the text route val.py:40-52 -> mergesingle / poly2origpoly / nmsbynamedict
+ * (DOTA_devkit/ResultMerge_multi_process.py:159-245) -> py_cpu_nms_poly_fast (:62-123), per class, for the chips of
+ * one scene.  Input is the detector's padded output: dets f32 [n_chips,K,6] (x, y, w, h, theta, score; contiguous),
+ * labels int32 [n_chips,K] (-1: no row), counts int32 [n_chips] (rows at or behind a chip's count are ignored),
+ * origins int32 [n_chips,2] (left, up), rates f64 [n_chips] or NULL (= 1.0).  Per row: the float32 polygon of
+ * rbox_to_poly widened to double, then (coordinate + origin) / rate in double (:178-185); rows are taken chip-major,
+ * then in detection order; score ties: ascending row.  A row is kept iff no kept higher row OF ITS CLASS has
+ * iou_poly > thresh (HBB prefilter :87-93).
+ * Outputs (capacity n_chips*K rows each, all on the device): out_polys f64 [.,8], out_scores f64, out_labels int64,
+ * out_src int64 (source row chip*K + k) -- compacted class-major, descending score inside a class; the rows behind
+ * the kept total are cleared (0 / -1).  class_counts int64 [num_classes].  status int64 [4]: [0] != 0 <=> the
+ * candidate pair list overflowed and THE OUTPUTS ARE NOT VALID, [1] candidate pairs found (run again with at least
+ * that pair_capacity), [2] suppression edges, [3] real input rows.
+ * pair_capacity <= 0: the default min(n(n-1)/2, max(32 n, 2^20)) + 1 with n = n_chips*K.  The workspace is
+ * O(n + pair_capacity): no n x n / 64 mask.  No host synchronisation, no device-to-host copy, no memset node: the call
+ * may be captured into a HIP graph. */
+size_t s2a_scene_merge_workspace_bytes(int64_t n_rows, int64_t pair_capacity);
+int s2a_scene_merge(const float* dets, const int32_t* labels, const int32_t* counts, const int32_t* origins,
+                    const double* rates, int64_t n_chips, int64_t K, int32_t num_classes, double thresh,
+                    int64_t pair_capacity, double* out_polys, double* out_scores, int64_t* out_labels,
+                    int64_t* out_src, int64_t* class_counts, int64_t* status, void* workspace,
+                    size_t workspace_bytes, s2a_stream_t stream);
+
 /* Convolution epilogue for the conv layers of the head/carrier that MIOpen runs without fusion:
  * y[positions, channels] (channels-last storage) = act(y + bias[c] (+ residual)), in place.
  * Replaces the bias add / residual add / ReLU passes that follow every nn.Conv2d of

@@ -13,6 +13,7 @@ from .alignconv import AlignConv, AlignConvFunction, align_conv
 from .orn import RotInvPoolFunction, rot_inv_pool, rot_inv_pool_backward
 from .loss import S2ANetLossFunction, s2anet_loss, grid_anchors
 from .fused import drop_weight_caches
+from .scene import tile_grid, chip_names, gather_chips, merge_detections, SceneDetections
 
 __all__ = [
     "box_iou_rotated", "nms_rotated", "ml_nms_rotated", "multiclass_nms_rotated",
@@ -20,4 +21,5 @@ __all__ = [
     "RotationInvariantPooling", "DeformConv", "DeformConvFunction", "deform_conv",
     "deform_conv_forward_cuda", "AlignConv", "AlignConvFunction", "align_conv", "RotInvPoolFunction", "rot_inv_pool",
     "rot_inv_pool_backward", "S2ANetLossFunction", "s2anet_loss", "grid_anchors", "drop_weight_caches",
+    "tile_grid", "chip_names", "gather_chips", "merge_detections", "SceneDetections",
 ]

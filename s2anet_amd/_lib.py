@@ -161,6 +161,10 @@ SYMBOLS = {
     "s2a_pyramid_candidates_count": (c_i64, [ctypes.POINTER(Pyramid), c_i64]),
     "s2a_pyramid_candidates": (c_int, [c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(Pyramid), c_int, c_i64, c_f32, c_vp, c_vp, c_vp, c_vp]),
     "s2a_rbox_to_poly": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp]),
+    "s2a_scene_gather_u8": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, ctypes.c_int32, c_vp, c_vp]),
+    "s2a_scene_merge_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "s2a_scene_merge": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, ctypes.c_int32, ctypes.c_double, c_i64,
+                                c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "s2a_delta2bbox_rotated": (c_int, [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp]),
     "s2a_fam_refine_anchors": (c_int, [c_vp, c_i64, c_i64, c_i64, c_f32, c_f32, c_int, c_int,
                                        c_vp, c_vp]),

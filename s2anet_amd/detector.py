@@ -262,6 +262,14 @@ class S2ANet(nn.Module):
             x = x.contiguous(memory_format=torch.channels_last)
         return self.head.get_bboxes_batched(self.features_to_pred(x), max_candidates, return_overflow, **nms_kw)
 
+    def detect_scene(self, scene_u8, batch=8, subsize=1024, gap=200, rate=1.0, thresh=0.5, return_chips=False, check=True,
+                     **detect_kw):
+        """a whole scene uint8 [H,W,3] on the device (or a list of (scene, rate) pairs) -> merged detections in scene
+        coordinates (``scene.SceneDetections``): tile grid of the reference's splitter, one gather launch per batch,
+        ``detect()`` in fixed batches, per-class polygon merge on the device -- see s2anet_amd/scene.py"""
+        from .scene import detect_scene
+        return detect_scene(self, scene_u8, batch, subsize, gap, rate, thresh, return_chips, check, **detect_kw)
+
 
 def load_reference_checkpoint(model, weights, map_location="cpu"):
     """val.py:153-183: a ``.pth`` file (or an already loaded dict) with a ``"state_dict"`` entry is

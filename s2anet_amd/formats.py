@@ -49,3 +49,22 @@ def task1_lines(img_name, det_bboxes, det_labels, class_names):
         out.setdefault(class_names[lb], []).append(
             "{} {:.4f} {:.4f} {:.4f} {:.4f} {:.4f} {:.4f} {:.4f} {:.4f} {:.4f}\n".format(stem, sc, *p))
     return out
+
+
+def merged_task1_lines(image_name, result, class_names):
+    """a merged scene (``scene.SceneDetections``, trimmed: ``check=True``) -> {class name: [lines]} in the format
+    mergesingle writes (DOTA_devkit/ResultMerge_multi_process.py:229-245): '<image> str(conf) str(x1) ... str(y4)',
+    no newline, in the order of the merged class file (descending score).  Classes without a row are absent."""
+    if int(result.status[0]) != 0:
+        raise RuntimeError("merged_task1_lines: the merge reported a pair-list overflow (status[0] != 0)")
+    counts = result.class_counts.cpu().tolist()
+    m = sum(counts)
+    polys = result.polys[:m].cpu().tolist()
+    scores = result.scores[:m].cpu().tolist()
+    stem = osp.splitext(image_name)[0]
+    out, at = {}, 0
+    for c, k in enumerate(counts):
+        if k:
+            out[class_names[c]] = [stem + " " + str(scores[i]) + " " + " ".join(map(str, polys[i])) for i in range(at, at + k)]
+        at += k
+    return out
