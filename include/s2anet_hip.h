@@ -92,6 +92,43 @@ int s2a_assign_labels(const float* anchors, int64_t num_anchors, const float* gt
                       int gt_max_assign_all, int filter_invalid_anchors, int filter_invalid_ious,
                       int64_t* assign_gt_ids, void* workspace, size_t workspace_bytes, s2a_stream_t stream);
 
+/* The same assignment for a whole batch and several anchor sets in ONE fixed launch sequence, with the image sort of
+ * the targets done on the device: no host read, no allocation, and a launch sequence and geometry that depend on the
+ * host arguments only, so the call can be captured into a graph and replayed against new targets.
+ *
+ *   sets[num_sets]   1 to 4 anchor sets of num_anchors anchors each; batch_stride (floats between two images' anchors) is
+ *                    0 for anchors shared by all images (the FAM grid anchors [A,5]) or >= 5 * A for per-image anchors
+ *                    (the ODM refined anchors [B,A,5]: A * 5)
+ *   targets          f32 [target_capacity,7] = (image, class, x, y, w, h, angle), px / rad, in ANY order.  The first
+ *                    *num_targets rows take part (num_targets: device scalar; NULL = all rows); a row whose image index
+ *                    (int64)targets[i,0] is outside [0, batch) is dropped, so such rows pad a static table
+ *   sorted_targets   [target_capacity,7]: the rows that take part, stably sorted by image (bit-equal to
+ *                    t[argsort(image, stable)]: rules 1 and 3 depend on the gt order); the rows behind them are zero.
+ *                    Must not alias targets
+ *   target_offsets   int64 [batch+1]: first sorted row of image b; [batch] = number of real rows
+ *   assign_ids       int64 [num_sets, batch, num_anchors]: s2a_assign_labels of (set, image) against that image's gts, the
+ *                    gt index counted within the image (what s2a_s2anet_loss_forward reads); an image without gts: valid
+ *                    anchors -1, the others -2.  Needs min_pos_iou_thr >= 0 and pos_iou_thr > 0
+ *   status           int64 [4]: [0] bit 0 = the pair list was too small (the ids are unspecified then, every write still
+ *                    stays inside the outputs), bit 1 = a per-image limit was exceeded (reserved: this implementation
+ *                    has none and never sets it); [1] = candidate pairs found, i.e. the pair_capacity a second call
+ *                    needs; [2] = real target rows; [3] = 0
+ *   pair_capacity    entries of the one pair list all (set, image) problems share (anchor-gt pairs that survive the circle
+ *                    and separating-axis tests); num_sets * num_anchors * target_capacity can never overflow
+ * workspace: s2a_assign_labels_batched_workspace_bytes of the same sizes (0 for sizes the call refuses), 16-byte aligned. */
+typedef struct s2a_anchor_set {
+  const float* anchors;
+  int64_t batch_stride;
+} s2a_anchor_set;
+size_t s2a_assign_labels_batched_workspace_bytes(int64_t num_sets, int64_t batch, int64_t num_anchors,
+                                                 int64_t target_capacity, int64_t pair_capacity);
+int s2a_assign_labels_batched(const s2a_anchor_set* sets, int num_sets, int64_t batch, int64_t num_anchors,
+                              const float* targets, int64_t target_capacity, const int64_t* num_targets, float img_h,
+                              float img_w, float pos_iou_thr, float neg_iou_thr, float min_pos_iou_thr,
+                              int gt_max_assign_all, int filter_invalid_anchors, int filter_invalid_ious,
+                              int64_t* assign_ids, float* sorted_targets, int64_t* target_offsets, int64_t* status,
+                              int64_t pair_capacity, void* workspace, size_t workspace_bytes, s2a_stream_t stream);
+
 /* Chip-merge polygon NMS: py_cpu_nms_poly_fast(dets[n,9] f64 = 8 polygon coordinates + score, thresh)
  * (DOTA_devkit/ResultMerge_multi_process.py:62-123) entirely on the device.  keep[] (n int64) receives
  * the surviving original indices in descending-score order, *count_dev their number; host_count as in
@@ -574,7 +611,8 @@ int s2a_stem_u8_f16(const void* image_u8, const void* weight_packed, const void*
 /* ---------------------------------------------------------------------------
  * S2ANet training loss: compute_loss -> compute_loss_single_level of the reference (models/head.py:353-646) for BOTH
  * modules (0 = FAM, 1 = ODM), all levels and all images in one forward call, after the assignment
- * (s2a_assign_labels, one call per image and module).
+ * (s2a_assign_labels_batched: both modules and all images in one sync-free launch sequence, so assignment + loss can be
+ * captured into one graph; or s2a_assign_labels, one call per image and module).
  *
  *   classification  focal BCE with logits (utils/loss.py:31-58): alpha factor t*alpha + (1-t)(1-alpha), modulating
  *                   factor (1 - p_t)^fl_gamma; positives: one-hot target on the gt's class, negatives: all-zero target,

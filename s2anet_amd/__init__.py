@@ -6,7 +6,7 @@ raises if the HIP library is missing or a tensor is not on the GPU.
 """
 from . import _lib  # noqa: F401
 from .rotated import (box_iou_rotated, nms_rotated, ml_nms_rotated, multiclass_nms_rotated,
-                      batched_multiclass_nms_rotated)
+                      batched_multiclass_nms_rotated, assign_labels, assign_labels_batched)
 from .orn import arf_forward, arf_backward, active_rotating_filter, ORConv2d, RotationInvariantPooling
 from .dcn import DeformConv, DeformConvFunction, deform_conv, deform_conv_forward_cuda
 from .alignconv import AlignConv, AlignConvFunction, align_conv
@@ -17,7 +17,7 @@ from .scene import tile_grid, chip_names, gather_chips, merge_detections, SceneD
 
 __all__ = [
     "box_iou_rotated", "nms_rotated", "ml_nms_rotated", "multiclass_nms_rotated",
-    "batched_multiclass_nms_rotated", "arf_forward", "arf_backward", "active_rotating_filter", "ORConv2d",
+    "batched_multiclass_nms_rotated", "assign_labels", "assign_labels_batched", "arf_forward", "arf_backward", "active_rotating_filter", "ORConv2d",
     "RotationInvariantPooling", "DeformConv", "DeformConvFunction", "deform_conv",
     "deform_conv_forward_cuda", "AlignConv", "AlignConvFunction", "align_conv", "RotInvPoolFunction", "rot_inv_pool",
     "rot_inv_pool_backward", "S2ANetLossFunction", "s2anet_loss", "grid_anchors", "drop_weight_caches",

@@ -64,6 +64,11 @@ class LossGradMap(ctypes.Structure):
     _fields_ = [("src", c_vp), ("dst", c_vp), ("numel", c_i64), ("dtype", ctypes.c_int32), ("norm_index", ctypes.c_int32)]
 
 
+class AnchorSet(ctypes.Structure):
+    """s2a_anchor_set: one anchor set of s2a_assign_labels_batched"""
+    _fields_ = [("anchors", c_vp), ("batch_stride", c_i64)]
+
+
 # every symbol include/s2anet_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "s2a_last_error": (ctypes.c_char_p, []),
@@ -76,6 +81,10 @@ SYMBOLS = {
     "s2a_assign_labels_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "s2a_assign_labels": (c_int, [c_vp, c_i64, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_int, c_int, c_int,
                                   c_vp, c_vp, c_sz, c_vp]),
+    "s2a_assign_labels_batched_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64, c_i64, c_i64]),
+    "s2a_assign_labels_batched": (c_int, [ctypes.POINTER(AnchorSet), c_int, c_i64, c_i64, c_vp, c_i64, c_vp, c_f32, c_f32,
+                                          c_f32, c_f32, c_f32, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp,
+                                          c_sz, c_vp]),
     "s2a_nms_poly_workspace_bytes": (c_sz, [c_i64]),
     "s2a_nms_poly": (c_int, [c_vp, c_i64, ctypes.c_double, c_vp, c_vp, ctypes.POINTER(c_i64), c_vp, c_sz, c_vp]),
     "s2a_nms_rotated_workspace_bytes": (c_sz, [c_i64, c_i64]),

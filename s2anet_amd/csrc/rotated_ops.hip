@@ -33,6 +33,7 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "assign_keys.hpp"
 #include "common.hpp"
 #include "rbox_geom.hpp"
 
@@ -3742,13 +3743,7 @@ extern "C" int s2a_box_iou_rotated(const float* boxes1, int64_t n, const float* 
 // lets later gts overwrite earlier ones, :131-145).
 namespace s2a {
 namespace {
-__device__ __forceinline__ int iou_key(float v) { return v < 0.f ? 0 : __float_as_int(v) + 1; }
-__device__ __forceinline__ float key_iou(int k) { return k == 0 ? -0.5f : __int_as_float(k - 1); }
-
-__device__ __forceinline__ bool anchor_valid(const float* __restrict__ a, float img_h, float img_w) {
-  return a[0] >= 0 && a[1] >= 0 && a[0] <= img_w && a[1] <= img_h && a[2] < img_w && a[3] < img_h;   // :63-69
-}
-
+// iou_key / key_iou / anchor_valid: assign_keys.hpp (shared with the batched form, assign_ops.hip)
 __global__ __launch_bounds__(256) void k_assign_rows(const float* __restrict__ anchors, float* __restrict__ ious,
                                                      int64_t M, int64_t N, float img_h, float img_w, float pos_thr,
                                                      float neg_thr, int filt_anchor, int filt_iou,

@@ -14,6 +14,7 @@ What changed against the reference glue (same results, no per-image / per-level 
 import math
 import os
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -21,7 +22,7 @@ from . import _lib
 from .alignconv import AlignConv
 from .loss import LOSS_DEFAULTS, grid_anchors, s2anet_loss
 from .orn import ORConv2d, RotationInvariantPooling
-from .rotated import assign_labels, batched_multiclass_nms_rotated, multiclass_nms_rotated
+from .rotated import assign_labels, assign_labels_batched, batched_multiclass_nms_rotated, multiclass_nms_rotated
 
 
 def delta2bbox_rotated(rois, deltas, wh_ratio_clip=16 / 1000):
@@ -284,15 +285,48 @@ class S2ANetHead(nn.Module):
             odm.append(assign_labels(refine_all[b], gt, imgs_size=self.imgs_size))
         return torch.stack([torch.stack(fam), torch.stack(odm)]), ts, offsets
 
+    def _core_loss(self, p, ids, ts, offsets):
+        return s2anet_loss(p[0], p[1], p[2], p[3], p[4], p[5], ids, ts, offsets, fl_gamma=self.fl_gamma,
+                           fl_alpha=self.fl_alpha, smoothL1_beta=self.smoothL1_beta, FPN_balance=self.FPN_balance,
+                           reg_balance=self.reg_balance, odm_balance=self.odm_balance)
+
+    def compute_loss_device(self, p, targets, num_targets=None, pair_capacity=None):
+        """compute_loss without any host read: the capturable form.  targets [G,7] in any order, rows with an image index
+        outside [0, B) are padding (a static table of a replayed graph); num_targets: optional int64 device scalar, only
+        the first num_targets rows take part.  One fixed launch sequence: the batched assignment of both modules and all
+        images (assign_labels_batched), then the fused loss.
+        -> (loss [1] f32, items [4] f32 = fam_cls, fam_reg, odm_cls, odm_reg, status [4] int64), all on the device.
+        status[0] != 0 means the result is NOT valid: bit 0 = the assignment's pair list was too small (status[1] is the
+        pair_capacity that fits), bit 1 = a per-image limit was exceeded; status[2] = target rows that took part."""
+        p = self._loss_pred(p)
+        B = p[1][0].shape[0]
+        init_all = torch.cat([a.reshape(-1, 5) for a in p[4]], 0)
+        refine_all = torch.cat([a.reshape(B, -1, 5) for a in p[5]], 1).detach()
+        ids, ts, offsets, status = assign_labels_batched((init_all, refine_all), targets, B, imgs_size=self.imgs_size,
+                                                         num_targets=num_targets, pair_capacity=pair_capacity)
+        loss, items = self._core_loss(p, ids, ts, offsets)
+        return loss, items, status
+
     def compute_loss(self, p, targets):
         """head.py:353-436: p = forward()'s 5 lists or the reference's 6; targets[N,7] (image, class, x, y, w, h,
         angle) in pixels / rad -> (loss [1] f32, loss_items float32 numpy [4] = fam_cls, fam_reg, odm_cls, odm_reg).
-        Host syncs: the target counts of the assignment and the loss_items read-back."""
+        One host sync: the loss_items read-back, which brings the assignment's status with it.  A pair list that was too
+        small (status bit 0) costs one more run at the capacity the first one reported; a per-image limit (bit 1) or
+        S2A_ASSIGN_BATCHED=0 takes the per-image route (assign_labels_fam_odm: a second sync and 2*B assign_labels
+        calls)."""
         p = self._loss_pred(p)
+        capacity = None
+        while os.environ.get("S2A_ASSIGN_BATCHED", "1") != "0":
+            loss, items, status = self.compute_loss_device(p, targets, pair_capacity=capacity)
+            host = torch.cat([items.detach().double(), status.double()]).cpu().numpy()     # the one host sync
+            flags = int(host[4])
+            if flags == 0:
+                return loss, host[:4].astype(np.float32)
+            if flags & 2 or capacity is not None:
+                break
+            capacity = int(host[5])
         ids, ts, offsets = self.assign_labels_fam_odm(p, targets)
-        loss, items = s2anet_loss(p[0], p[1], p[2], p[3], p[4], p[5], ids, ts, offsets, fl_gamma=self.fl_gamma,
-                                  fl_alpha=self.fl_alpha, smoothL1_beta=self.smoothL1_beta, FPN_balance=self.FPN_balance,
-                                  reg_balance=self.reg_balance, odm_balance=self.odm_balance)
+        loss, items = self._core_loss(p, ids, ts, offsets)
         return loss, items.detach().cpu().numpy()
 
     # ------------------------------------------------------------------ decode + NMS, batched

@@ -2,8 +2,11 @@
 
 ``s2anet_loss`` is the capture-safe core: one autograd Function over both modules, all levels and all images
 (csrc/loss_ops.hip).  Forward = 2 launches, backward = 1 launch, no host synchronisation: the positive counts, the
-max(npos, B) normalisers and the balances stay on the device.  The assignment (s2a_assign_labels, one call per image
-and module) and the image sort of the targets are done by ``S2ANetHead.assign_labels_fam_odm``.
+max(npos, B) normalisers and the balances stay on the device.  The assignment and the image sort of the targets come
+from ``assign_labels_batched`` (s2a_assign_labels_batched: both modules and all images in one sync-free launch sequence),
+so ``S2ANetHead.compute_loss_device`` = assignment + this core is capturable as a whole and replays against new targets
+written into a static table; ``S2ANetHead.assign_labels_fam_odm`` (s2a_assign_labels, one call per image and module,
+one host read of the target counts) is the per-image form of the same ids.
 
 Maps are read in their NCHW layout; a map in another layout (channels_last) is copied to NCHW first.
 """

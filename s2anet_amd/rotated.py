@@ -91,6 +91,61 @@ def assign_labels(anchors, gt_boxes, imgs_size=(1024, 1024), pos_iou_thr=0.5, ne
     return out
 
 
+ASSIGN_PAIR_CAPACITY = 4 << 20       # default ceiling of the batched assignment's pair list (12 B per entry)
+
+
+def assign_labels_batched(anchor_sets, targets, batch, imgs_size=(1024, 1024), pos_iou_thr=0.5, neg_iou_thr=0.4,
+                          min_pos_iou_thr=0, gt_max_assign_all=True, filter_invalid_anchors=True,
+                          filter_invalid_ious=True, num_targets=None, pair_capacity=None):
+    """assign_labels for every (anchor set, image) of a batch in one fixed, sync-free launch sequence
+    (s2a_assign_labels_batched): capturable, and replayable against new targets written into the same table.
+
+    anchor_sets: 1 to 4 tensors, each [A,5] (shared by all images) or [batch,A,5]; targets: [G,7] = (image, class, x, y,
+    w, h, angle) in px / rad, any order, rows with an image index outside [0, batch) are padding; num_targets: optional
+    int64 device scalar, only the first num_targets rows take part; pair_capacity: entries of the shared candidate pair
+    list, default min(S * A * G, ASSIGN_PAIR_CAPACITY).
+    -> (assign_ids int64 [S,batch,A] (-2 ignore, -1 negative, >= 0 gt index within the image), sorted_targets f32 [G,7]
+    (by image, stable; zero behind the real rows), target_offsets int64 [batch+1], status int64 [4]: [0] bit 0 = pair list
+    too small (ids unspecified), bit 1 = per-image limit exceeded; [1] pairs found; [2] real rows; [3] 0).
+    All four stay on the device; nothing is read back."""
+    sets = list(anchor_sets)
+    _lib.require_cuda(targets, num_targets, *sets)
+    S, B = len(sets), int(batch)
+    if not 1 <= S <= 4:
+        raise ValueError(f"1 to 4 anchor sets, got {S}")
+    dev = sets[0].device
+    sets = [a.detach().float().contiguous() for a in sets]
+    A = sets[0].shape[-2]
+    table = (_lib.AnchorSet * S)()
+    for e, a in zip(table, sets):
+        if a.shape == (A, 5):
+            e.batch_stride = 0
+        elif a.shape == (B, A, 5):
+            e.batch_stride = A * 5
+        else:
+            raise ValueError(f"anchor sets must be [{A},5] or [{B},{A},5], got {tuple(a.shape)}")
+        e.anchors = a.data_ptr()
+    t = targets.detach().float().reshape(-1, 7).contiguous()
+    G = t.shape[0]
+    if num_targets is not None and (num_targets.dtype != torch.int64 or num_targets.numel() != 1):
+        raise ValueError("num_targets must be an int64 device scalar")
+    P = min(S * A * G, ASSIGN_PAIR_CAPACITY) if pair_capacity is None else int(pair_capacity)
+    ids = torch.empty((S, B, A), dtype=torch.int64, device=dev)
+    ts = torch.empty((G, 7), dtype=torch.float32, device=dev)
+    offsets = torch.empty((B + 1,), dtype=torch.int64, device=dev)
+    status = torch.empty((4,), dtype=torch.int64, device=dev)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        ws = _lib.workspace(L.s2a_assign_labels_batched_workspace_bytes(S, B, A, G, P), dev, "assign_batched")
+        _lib.check(L.s2a_assign_labels_batched(table, S, B, A, _lib.ptr(t) if G else None, G, _lib.ptr(num_targets),
+                                               float(imgs_size[0]), float(imgs_size[1]), float(pos_iou_thr),
+                                               float(neg_iou_thr), float(min_pos_iou_thr), int(bool(gt_max_assign_all)),
+                                               int(bool(filter_invalid_anchors)), int(bool(filter_invalid_ious)),
+                                               _lib.ptr(ids), _lib.ptr(ts) if G else None, _lib.ptr(offsets),
+                                               _lib.ptr(status), P, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+    return ids, ts, offsets, status
+
+
 def nms_poly(dets, thresh=0.5):
     """py_cpu_nms_poly_fast (DOTA_devkit/ResultMerge_multi_process.py:62-123) on the GPU:
     dets[n,9] = x1,y1,...,x4,y4,score -> kept indices (int64), descending score"""

@@ -3,6 +3,10 @@
 same batch):
   (a) the core: s2anet_loss forward + backward (3 launches, no host sync)
   (b) the whole S2ANetHead.compute_loss forward + backward, assignment (2*B assign_labels calls) included
+  (d) the assignment alone, per-image route (S2ANetHead.assign_labels_fam_odm) and batched route (assign_labels_batched);
+      compute_loss forward + backward with S2A_ASSIGN_BATCHED=0 and with the batched route; compute_loss_device +
+      backward replayed from a captured graph.  The routes are interleaved in one process, three repetitions each:
+      median of the repetitions' medians and their range
   (c) the reference's algorithm (models/head.py:353-646) restated with torch ops on the same GPU tensors: per level
       boolean-mask indexing, .item() counts, FocalLoss / SmoothL1Loss, autograd backward
 Prints one JSON line; median wall time per iteration in microseconds (CUDA events, after warm-up)."""
@@ -90,6 +94,17 @@ def timed(fn, steps, warmup):
     return times[len(times) // 2]
 
 
+def interleaved(rows, steps, warmup, reps=3):
+    """rows: name -> fn.  Every repetition times every row (A, B, ..., A, B, ...): -> name -> {median, min, max} over the
+    repetitions' medians"""
+    got = {k: [] for k in rows}
+    for _ in range(reps):
+        for k, fn in rows.items():
+            got[k].append(timed(fn, steps, warmup))
+    return {k: {"median": round(sorted(v)[len(v) // 2], 1), "min": round(min(v), 1), "max": round(max(v), 1)}
+            for k, v in got.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=50)
@@ -119,6 +134,52 @@ def main():
            "core_fwd_bwd": round(timed(core, args.steps, args.warmup), 1),
            "compute_loss_fwd_bwd": round(timed(whole, args.steps, args.warmup), 1),
            "reference_form_fwd_bwd": round(timed(reference, max(args.steps // 5, 3), 2), 1)}
+    # (d) the two assignment routes, A/B in one process
+    from s2anet_amd import assign_labels_batched
+    from s2anet_amd.rotated import ASSIGN_PAIR_CAPACITY
+    B = p[1][0].shape[0]
+
+    def assign_batched():
+        init_all = torch.cat([a.reshape(-1, 5) for a in p[4]], 0)
+        refine_all = torch.cat([a.reshape(B, -1, 5) for a in p[5]], 1)
+        return assign_labels_batched((init_all, refine_all), t, B, imgs_size=head.imgs_size)
+
+    def route(value):
+        def fn():
+            os.environ["S2A_ASSIGN_BATCHED"] = value
+            loss, _ = head.compute_loss(p, t)
+            torch.autograd.grad(loss, maps)
+        return fn
+
+    def device_step():
+        loss, items, status = head.compute_loss_device(p, t)
+        return (loss, items, status, *torch.autograd.grad(loss, maps))
+
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(2):
+            device_step()
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        static = device_step()
+    prior = os.environ.get("S2A_ASSIGN_BATCHED")
+    ab = interleaved({"assign_per_image": lambda: head.assign_labels_fam_odm(p, t), "assign_batched": assign_batched,
+                      "compute_loss_per_image_fwd_bwd": route("0"), "compute_loss_batched_fwd_bwd": route("1"),
+                      "compute_loss_device_graph_replay": graph.replay}, args.steps, args.warmup)
+    if prior is None:
+        os.environ.pop("S2A_ASSIGN_BATCHED", None)
+    else:
+        os.environ["S2A_ASSIGN_BATCHED"] = prior
+    res.update(ab)
+    ids_b, _, _, status = assign_batched()
+    graph.replay()
+    torch.cuda.synchronize()
+    res["assign_pairs_found"] = int(status[1])
+    res["assign_pair_capacity_default"] = min(2 * ids.shape[2] * t.shape[0], ASSIGN_PAIR_CAPACITY)
+    res["assign_routes_equal"] = bool(torch.equal(ids_b, ids)) and int(status[0]) == 0
+    res["graph_replay_equals_eager"] = all(bool(torch.equal(a, b)) for a, b in zip(static, device_step()))
     l1, it1 = head.compute_loss(p, t)
     _, it2 = reference_form(head, p, ts, ids)
     res["items_core"] = [float(v) for v in it1]
