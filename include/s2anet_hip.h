@@ -414,6 +414,54 @@ int s2a_scene_merge(const float* dets, const int32_t* labels, const int32_t* cou
                     int64_t* out_src, int64_t* class_counts, int64_t* status, void* workspace,
                     size_t workspace_bytes, s2a_stream_t stream);
 
+/* ---- DOTA Task-1 evaluation of all classes on the device (eval_ops.hip) ----
+ *
+ * Replaces the loop of val.py:332-399: voc_eval (DOTA_devkit/dota_evaluation_task1.py:92-318) once per class, then the
+ * max-F1 point of every curve (val.py:357-386).  Everything is on the device:
+ *   detections    det_polys f64 [D,8], det_scores f64 [D], det_labels int32 [D], det_image int32 [D]
+ *   ground truth  gt_polys f64 [G,8], gt_labels int32 [G], gt_image int32 [G], gt_difficult uint8 [G]
+ * A row of either side is PADDING when its label is outside [0, num_classes) or its image is outside [0, num_images):
+ * it is ignored and its polygon and score are never interpreted (NaN is harmless), so a static table or the detector's
+ * -1 padded output is evaluated without compaction.
+ * Order (:183 per class): class-major, descending score, equal scores (-0 == +0) by ascending input row.  Per detection
+ * (:204-263): the first maximum of iou_poly(GT, det) over the ground truths of its class and image, in input order, that
+ * pass the +1-pixel axis-aligned prefilter (:223-252) -- the values of s2a_polyiou_match.  TP/FP (:265-290) as a parallel
+ * rule: a detection with ovmax > ovthresh whose ground truth is not a filtered difficult box QUALIFIES for it; of the
+ * detections that qualify for one ground truth the first in the order is the TP, the others are FP; a match with a filtered
+ * difficult box is neither; everything else is FP.  rec = tp / npos, prec = tp / max(tp + fp, eps) (:301-309), AP by the
+ * 11-point rule (:62-70; thresholds11 = the 11 doubles of np.arange(0.0, 1.1, 0.1), a HOST array read during the call;
+ * may be NULL when use_07_metric == 0) or the area rule (:72-88); f1 = 2 rec prec / (rec + prec + 1e-16), first maximum.
+ * Outputs per class [num_classes]: ap, precision, recall, f1, conf (at the max-F1 point) f64; num_det_at_f1 (its index
+ * + 1), npos (ground truths that count: all when is_filter_difficult == 0), ndet int64; valid uint8.
+ *   - a class without detections reports zeros (:322) with num_det_at_f1 = 0;
+ *   - a class with npos == 0 (the reference exits or divides by zero) reports zeros with valid = 0; otherwise valid = 1.
+ * curves (may be NULL, and so may each member): one entry per position of the order, capacity D; entries behind the last
+ * real detection are cleared (0, order / argmax -1).  order = source row, argmax = input ground-truth row or -1, ovmax =
+ * -inf when no ground truth passed the prefilter, tp_cum / fp_cum / rec / prec = the class's curve, seg_start
+ * [num_classes + 1] = first position of every class (last entry: number of real detections).
+ * One fixed launch sequence: no host synchronisation, no device-to-host copy, no memset node -- the call may be captured
+ * into a HIP graph.  Integer atomics only, every sum in a fixed order: two runs give the same bits.  Workspace
+ * O(D + G + num_classes * num_images), no D x G array.  D, G < 2^31; num_classes <= 1024;
+ * (num_classes + 1) * num_images < 2^31. */
+typedef struct {
+  int64_t* order;
+  double* ovmax;
+  int64_t* argmax;
+  int64_t* tp_cum;
+  int64_t* fp_cum;
+  double* rec;
+  double* prec;
+  int64_t* seg_start;
+} s2a_eval_curves;
+size_t s2a_eval_task1_workspace_bytes(int64_t num_dets, int64_t num_gts, int32_t num_classes, int32_t num_images);
+int s2a_eval_task1(const double* det_polys, const double* det_scores, const int32_t* det_labels, const int32_t* det_image,
+                   int64_t num_dets, const double* gt_polys, const int32_t* gt_labels, const int32_t* gt_image,
+                   const uint8_t* gt_difficult, int64_t num_gts, int32_t num_classes, int32_t num_images, double ovthresh,
+                   int is_filter_difficult, int use_07_metric, const double* thresholds11, double* ap, double* precision,
+                   double* recall, double* f1, double* conf, int64_t* num_det_at_f1, int64_t* npos, int64_t* ndet,
+                   uint8_t* valid, const s2a_eval_curves* curves, void* workspace, size_t workspace_bytes,
+                   s2a_stream_t stream);
+
 /* Convolution epilogue for the conv layers of the head/carrier that MIOpen runs without fusion:
  * y[positions, channels] (channels-last storage) = act(y + bias[c] (+ residual)), in place.
  * Replaces the bias add / residual add / ReLU passes that follow every nn.Conv2d of

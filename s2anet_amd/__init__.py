@@ -14,6 +14,7 @@ from .orn import RotInvPoolFunction, rot_inv_pool, rot_inv_pool_backward
 from .loss import S2ANetLossFunction, s2anet_loss, grid_anchors
 from .fused import drop_weight_caches
 from .scene import tile_grid, chip_names, gather_chips, merge_detections, SceneDetections
+from .evaluate import evaluate_task1, Task1Evaluator, Task1Result, claim_tp_fp
 
 __all__ = [
     "box_iou_rotated", "nms_rotated", "ml_nms_rotated", "multiclass_nms_rotated",
@@ -22,4 +23,5 @@ __all__ = [
     "deform_conv_forward_cuda", "AlignConv", "AlignConvFunction", "align_conv", "RotInvPoolFunction", "rot_inv_pool",
     "rot_inv_pool_backward", "S2ANetLossFunction", "s2anet_loss", "grid_anchors", "drop_weight_caches",
     "tile_grid", "chip_names", "gather_chips", "merge_detections", "SceneDetections",
+    "evaluate_task1", "Task1Evaluator", "Task1Result", "claim_tp_fp",
 ]

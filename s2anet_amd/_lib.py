@@ -64,6 +64,12 @@ class LossGradMap(ctypes.Structure):
     _fields_ = [("src", c_vp), ("dst", c_vp), ("numel", c_i64), ("dtype", ctypes.c_int32), ("norm_index", ctypes.c_int32)]
 
 
+class EvalCurves(ctypes.Structure):
+    """s2a_eval_curves: optional per-position outputs of s2a_eval_task1 (NULL members are not written)"""
+    _fields_ = [("order", c_vp), ("ovmax", c_vp), ("argmax", c_vp), ("tp_cum", c_vp), ("fp_cum", c_vp), ("rec", c_vp),
+                ("prec", c_vp), ("seg_start", c_vp)]
+
+
 class AnchorSet(ctypes.Structure):
     """s2a_anchor_set: one anchor set of s2a_assign_labels_batched"""
     _fields_ = [("anchors", c_vp), ("batch_stride", c_i64)]
@@ -174,6 +180,10 @@ SYMBOLS = {
     "s2a_scene_merge_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "s2a_scene_merge": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, ctypes.c_int32, ctypes.c_double, c_i64,
                                 c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "s2a_eval_task1_workspace_bytes": (c_sz, [c_i64, c_i64, ctypes.c_int32, ctypes.c_int32]),
+    "s2a_eval_task1": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_int32, ctypes.c_int32,
+                               ctypes.c_double, c_int, c_int, ctypes.POINTER(ctypes.c_double)] + [c_vp] * 9 +
+                       [ctypes.POINTER(EvalCurves), c_vp, c_sz, c_vp]),
     "s2a_delta2bbox_rotated": (c_int, [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp]),
     "s2a_fam_refine_anchors": (c_int, [c_vp, c_i64, c_i64, c_i64, c_f32, c_f32, c_int, c_int,
                                        c_vp, c_vp]),
