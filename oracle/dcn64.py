@@ -22,20 +22,20 @@ import torch
 _F64 = torch.float64
 
 
-def sample_points(offset, pos_dtype=None):
-    """offset [B,18,H,W] -> (h, w) [B,9,H,W] float64, the sample points.  pos_dtype=torch.float32 rounds them the way a
+def sample_points(offset, pos_dtype=None, dtype=_F64):
+    """offset [B,18,H,W] -> (h, w) [B,9,H,W] in `dtype` (float64), the sample points.  pos_dtype=torch.float32 rounds them the way a
     float32 kernel forms them, fl32(float(y - 1 + i) + dy) (deform_conv_cuda_kernel.cu:222-223 at scalar_t = float,
     and every kernel of csrc/dcn_bwd_ops.hip); d(point)/d(offset) stays 1."""
     B, _, H, W = offset.shape
     dev = offset.device
     t = torch.arange(9, device=dev)
-    base_h = (torch.arange(H, device=dev, dtype=_F64).view(1, H, 1) - 1 + (t // 3).to(_F64).view(9, 1, 1)).expand(9, H, W)
-    base_w = (torch.arange(W, device=dev, dtype=_F64).view(1, 1, W) - 1 + (t % 3).to(_F64).view(9, 1, 1)).expand(9, H, W)
-    off = offset.to(_F64)
+    base_h = (torch.arange(H, device=dev, dtype=dtype).view(1, H, 1) - 1 + (t // 3).to(dtype).view(9, 1, 1)).expand(9, H, W)
+    base_w = (torch.arange(W, device=dev, dtype=dtype).view(1, 1, W) - 1 + (t % 3).to(dtype).view(9, 1, 1)).expand(9, H, W)
+    off = offset.to(dtype)
     h, w = base_h + off[:, 0::2], base_w + off[:, 1::2]
     if pos_dtype is not None:
-        h = h + (h.detach().to(pos_dtype).to(_F64) - h.detach())
-        w = w + (w.detach().to(pos_dtype).to(_F64) - w.detach())
+        h = h + (h.detach().to(pos_dtype).to(dtype) - h.detach())
+        w = w + (w.detach().to(pos_dtype).to(dtype) - w.detach())
     return h, w
 
 
@@ -60,17 +60,22 @@ def _columns(xf, corners):
     """xf [Cc, H*W] of one image, corners of its [9,H,W] points -> columns [Cc, 9*H*W]"""
     cols = None
     for idx, wt, _ in corners:
-        v = xf[:, idx.reshape(-1)] * wt.reshape(1, -1)
+        v = xf[:, idx.reshape(-1)] * wt.reshape(1, -1).to(xf.dtype)
         cols = v if cols is None else cols + v
     return cols
 
 
-def deform_conv64(x, offset, weight, pos_dtype=None):
-    """differentiable forward, float64, no chunking (small shapes): -> out [B,O,H,W]"""
+def deform_conv64(x, offset, weight, pos_dtype=None, dtype=_F64):
+    """differentiable forward, no chunking (small shapes): -> out [B,O,H,W].  dtype: the type every step runs in, float64
+    for the reference; the same stock ops in float32 / float16 are the baseline a kernel's error is compared with
+    (oracle/twin64.py)"""
     B, C, H, W = x.shape
     O = weight.shape[0]
-    h, w = sample_points(offset, pos_dtype)
-    xx, ww = x.to(_F64), weight.to(_F64).reshape(O, C * 9)
+    # float16: the sample points and the bilinear weights are formed in float32 (no float16 kernel of this package forms
+    # positions in float16: at a coordinate of 16-32 its ulp is 0.016 px) and the weights are rounded to float16 once,
+    # so that the float16 baseline is a single-rounding computation on the same points
+    h, w = sample_points(offset, pos_dtype, torch.float32 if dtype == torch.float16 else dtype)
+    xx, ww = x.to(dtype), weight.to(dtype).reshape(O, C * 9)
     outs = []
     for b in range(B):
         corners, _ = _corners(h[b], w[b], H, W)

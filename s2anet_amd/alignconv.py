@@ -143,7 +143,8 @@ class AlignConv(nn.Module):
     def forward(self, x, anchors, stride):
         num_imgs, H, W = anchors.shape[:3]
         if self.fused_ok(x):
-            if not (torch.is_grad_enabled() and self.deform_conv.weight.requires_grad):
+            # the packed-filter launch has no backward: taken only when neither x nor the filter wants a gradient
+            if not (torch.is_grad_enabled() and (x.requires_grad or self.deform_conv.weight.requires_grad)):
                 return align_conv_forward(x, anchors, self.packed_weight(x.dtype), stride, relu=True, packed=True,
                                           out_channels=self.deform_conv.out_channels)
             return align_conv(x, anchors, self.deform_conv.weight, stride)

@@ -9,23 +9,40 @@ import torch.nn.functional as F
 from . import _lib
 
 
+def _needs_grad(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
 def bias_act_(y, bias, residual=None, relu=False, out=None):
-    """in place: y = act(y + bias[c] (+ residual)); y must be channels-last contiguous.
-    out: a dense NHWC buffer of y's shape that receives the result instead (e.g. a level slice of a pyramid-packed tensor)"""
+    """y = act(y + bias[c] (+ residual)): in place in ONE pass (s2a_bias_act_nhwc) when y is channels-last contiguous
+    with whole 16-byte channel vectors, stock ops otherwise.
+    out: a dense NHWC buffer of y's shape that receives the result instead (e.g. a level slice of a pyramid-packed tensor).
+    The raw pass writes through a pointer, which autograd cannot see: when grad is enabled and y, bias or residual
+    requires grad, the stock ops run instead (bias gradient, ReLU mask and residual gradient are autograd's), whatever
+    the layout, and out= is refused."""
     _lib.require_cuda(y, bias, residual)
     B, C, H, W = y.shape
     if out is not None:
         assert out.shape == y.shape and out.dtype == y.dtype and out.permute(0, 2, 3, 1).is_contiguous()
-    ok = (y.is_contiguous(memory_format=torch.channels_last) and
+    grad = _needs_grad(y, bias, residual)
+    if grad and out is not None:
+        raise RuntimeError("bias_act_(out=...) writes a caller's buffer and has no backward: call it under torch.no_grad()")
+    ok = (not grad and y.is_contiguous(memory_format=torch.channels_last) and
           C % (8 if y.dtype == torch.float16 else 4) == 0 and y.dtype in (torch.float16, torch.float32) and
           (residual is None or (residual.shape == y.shape and residual.dtype == y.dtype and
                                 residual.is_contiguous(memory_format=torch.channels_last))))
-    if not ok:      # odd channel count / NCHW storage: stock ops (still on the GPU)
+    if not ok:      # odd channel count / NCHW storage / a gradient is wanted: stock ops (still on the GPU)
         y = y + bias.view(1, -1, 1, 1).to(y.dtype)
         if residual is not None:
             y = y + residual
         y = F.relu(y) if relu else y
         return y if out is None else out.copy_(y)
+    return _bias_act_raw(y, bias, residual, relu, out)
+
+
+def _bias_act_raw(y, bias, residual=None, relu=False, out=None):
+    """the one-pass epilogue itself, no checks: writes y (or out) through its pointer, invisible to autograd"""
+    B, C, H, W = y.shape
     b = bias if bias.dtype == y.dtype and bias.is_contiguous() else bias.to(y.dtype).contiguous()
     with torch.cuda.device(y.device):
         _lib.check(_lib.lib().s2a_bias_act_nhwc_to(_lib.ptr(y), _lib.ptr(b), _lib.ptr(residual),
@@ -322,6 +339,8 @@ class FusedConv2d(nn.Conv2d):
             if residual is not None:
                 y = y + residual
             return F.relu(y) if self.fuse_relu else y
+        # library convolution + epilogue: the raw one-pass epilogue when no gradient is wanted, stock (differentiable) ops
+        # when grad is enabled and x, the filter, the bias or the residual requires grad (bias_act_ decides)
         y = F.conv2d(x, self.weight, None, self.stride, self.padding, self.dilation, self.groups)
         return bias_act_(y, self.bias, residual, self.fuse_relu)
 

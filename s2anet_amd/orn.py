@@ -151,6 +151,8 @@ class _ActiveRotatingFilter(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_output):
         indices, = ctx.saved_tensors
+        if grad_output.dtype in (torch.float16, torch.bfloat16):      # the kernel sums in float32 / float64 only (as the
+            return arf_backward(indices, grad_output.float()).to(grad_output.dtype), None   # reference): one rounding
         return arf_backward(indices, grad_output), None
 
 
