@@ -591,6 +591,18 @@ int s2a_conv3x3_tail1x1_f16(const void* x, const void* weight_frag, const void* 
                             int64_t mid_channels, int64_t out_channels, int64_t height, int64_t width,
                             s2a_stream_t stream);
 
+/* A bottleneck's conv3 and the NEXT bottleneck's conv1 in one launch (models/backbone.py:69-83 with the BatchNorms
+ * folded: conv3 + bn3 + residual + relu, then the next block's conv1 + bn1 + relu):
+ *   out       [B,H,W,O]  = relu(W . x + b + residual)        x [B,H,W,K], f16 NHWC, residual [B,H,W,O] or NULL
+ *   chain_out [B,H,W,O3] = relu(Wc . out + bc)               computed from the finished rows inside the workgroup
+ * Both results are bit-identical to the two s2a_conv_nhwc_f16 (1x1) launches; the block output is not read back.
+ * weight_frag / chain_weight_frag from s2a_conv_pack_weight_f16 (ksize 1).  (channels, out_channels, chain_channels) =
+ * (128, 512, 128), (128, 512, 256) or (256, 1024, 256); the chain filter, bias and output are required. */
+int s2a_conv1x1_chain_f16(const void* x, const void* weight_frag, const void* bias, const void* residual, void* out,
+                          const void* chain_weight_frag, const void* chain_bias, void* chain_out, int64_t chain_channels,
+                          int64_t batch, int64_t channels, int64_t out_channels, int64_t height, int64_t width,
+                          s2a_stream_t stream);
+
 /* FPN top-down step in one launch (models/neck.py:67-79): out[B,H,W,O] = conv1x1(x[B,H,W,C]) + bias +
  * nearest-2x-upsample(coarse[B,H/2,W/2,O]); f16 channels-last, H and W even, C and O multiples of 64. */
 int s2a_conv1x1_add_up2_f16(const void* x, const void* weight_frag, const void* bias, const void* coarse,

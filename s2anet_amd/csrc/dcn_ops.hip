@@ -2025,6 +2025,261 @@ __global__ __launch_bounds__(256 * PH, PH == 1 ? 2 : 1) void k_conv_f16(const _F
 #endif
 }
 
+// ------------------------------------------------------------------ 1x1 + residual + ReLU with the next block's conv1 chained
+// A bottleneck's conv3 (1x1, K -> O = 4 K, + bias + residual + ReLU, models/backbone.py:69-83) and the NEXT bottleneck's
+// conv1 (1x1, O -> O3, + bias + ReLU) in one launch: the block output is written once and not read back by a second
+// launch.  A workgroup (4 waves, 64 consecutive positions) owns ALL O channels of its positions: the input tile (K <= 256:
+// up to four 64-channel chunks at the 144-byte pixel pitch) stays in LDS, and the 256-map output groups are walked one
+// after the other -- GEMM (wave = 64 maps x 64 positions), rows staged through LDS (528-byte pitch), residual + ReLU,
+// whole-row stores, finished rows back to LDS, then this group's 256-channel K-slice of the chained GEMM into accumulators
+// that live across the groups.  <= 72 KB of LDS and <= 256 registers: two workgroups per CU, one's memory passes under the
+// other's MFMAs.
+// Both results are bit-identical to the stand-alone launches of k_conv_f16: the main GEMM and a chained layer of 256 / 512
+// maps use its 16x16x32 fragments (the full-width 1x1 form), a chained layer of 128 maps its 32x32x16 form (OG = 2); the
+// accumulation order over the input channels is ascending in both, and the epilogue roundings are the same
+// (rnd16(rnd16(acc + b) + r), ReLU on the rounded halves).
+template <int CC, int O3>
+__global__ __launch_bounds__(256, 2) void k_conv1x1_chain_f16(const _Float16* __restrict__ x,
+                                                              const _Float16* __restrict__ wfrag,
+                                                              const _Float16* __restrict__ bias,
+                                                              const _Float16* __restrict__ residual,
+                                                              _Float16* __restrict__ out,
+                                                              const _Float16* __restrict__ chain_w,
+                                                              const _Float16* __restrict__ chain_b,
+                                                              _Float16* __restrict__ chain_out, int64_t Ntot,
+                                                              unsigned x_bytes) {
+  using T = _Float16;
+  using V = f16x8;
+  using h2e = __attribute__((ext_vector_type(2))) _Float16;
+  using h4e = __attribute__((ext_vector_type(4))) _Float16;
+  constexpr int kPos = 64, kChunkB = kPos * kRowBytes, kStRowB = 528;
+  constexpr bool C16 = O3 >= 256;               // chained layer on 16x16x32 fragments (stand-alone: OG = 4)
+  constexpr int NG3 = C16 ? O3 / 256 : 1;       // 64-map groups of the chained layer per wave
+  constexpr int G3 = O3 / 64;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+  const int64_t tile = xcd_remap(blockIdx.x, gridDim.x);
+  const int64_t g0 = tile * kPos;
+  constexpr int K = 64 * CC, O = 4 * K, NG = O / 256, G = O / 64;     // (a bottleneck's conv3: O = 4 K)
+  char* s_x = smem;
+  char* s_st = smem + CC * kChunkB;
+  T* s_bias = reinterpret_cast<T*>(s_st + kPos * kStRowB);
+
+  // input tile -> LDS by LDS-DMA, every chunk at once (layout and zero fill: k_conv_f16's TAPS = 1 patch)
+  {
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(x), 0, (int)x_bytes, 0x00020000);
+    unsigned pvoff[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      const int v = (wave_u + 4 * j) * 64 + lane, p = v / 9, q = v % 9;
+      const bool in = q < 8 && p < kPos && g0 + p < Ntot;
+      pvoff[j] = in ? (unsigned)((g0 + p) * K * 2 + q * 16) : 0x80000000u;
+    }
+#pragma unroll
+    for (int cc = 0; cc < CC; cc++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        const int i = wave_u + 4 * j;
+        if (i < 9)
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)(s_x + cc * kChunkB + i * 1024), 16,
+                                                   (int)pvoff[j], cc * 128, 0, 0);
+      }
+  }
+
+  // 16x16x32 lane maps and fragment addresses: k_conv_f16
+  const int kg16 = lane >> 4, i16 = lane & 15;
+  const int pix16 = (i16 >= 4 && i16 < 12) ? (((i16 - 4) >> 1) * 4 + (i16 & 1))
+                                           : (((i16 & 3) >> 1) * 4 + 2 + (i16 & 1) + (i16 >= 12 ? 8 : 0));
+  const int bofs = (kg16 & 1) * 64 + (kg16 >> 1) * 16;
+  const int wlane = ((lane >> 4) & 1) * 128 + (lane >> 5) * 32 + (lane & 15);
+  // filter fragments one k-step (half a 64-channel chunk) at a time: the four 16-map tiles of group g, stage s
+  auto load_w16 = [&](const T* wf, int s, int Gn, int g, int ks, V (&wv)[4]) {
+    const V* p = reinterpret_cast<const V*>(wf) + ((int64_t)s * Gn + g) * 8 * 64 + wlane + ks * 64;
+#pragma unroll
+    for (int a = 0; a < 4; a++) wv[a] = p[(a >> 1) * 4 * 64 + (a & 1) * 16];
+  };
+  // one k-step: 64 maps x 64 positions of this wave; brow = the lane's B row of the first 16-position tile
+  auto mma16 = [&](const char* brow, int tile_b, int ks, const V (&wv)[4], f32x4 (&acc)[4][4]) {
+    V pf[4];
+#pragma unroll
+    for (int b = 0; b < 4; b++) pf[b] = *reinterpret_cast<const V*>(brow + b * tile_b + ks * 32);
+#pragma unroll
+    for (int a = 0; a < 4; a++)
+#pragma unroll
+      for (int b = 0; b < 4; b++) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wv[a], pf[b], acc[a][b], 0, 0, 0);
+  };
+
+  // accumulators of the chained layer, live across the output groups
+  f32x4 cacc[C16 ? NG3 : 1][4][4];
+  f32x16 c2[2];
+  if constexpr (C16) {
+#pragma unroll
+    for (int n = 0; n < NG3; n++)
+#pragma unroll
+      for (int a = 0; a < 4; a++)
+#pragma unroll
+        for (int b = 0; b < 4; b++)
+#pragma unroll
+          for (int r = 0; r < 4; r++) cacc[n][a][b][r] = 0.f;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) c2[j][r] = 0.f;
+  }
+  const bool has_res = residual != nullptr;
+  const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(has_res ? residual : out), 0,
+                                                                      (int)((uint64_t)Ntot * O * 2), 0x00020000);
+  const int pos0 = tid >> 5, col0 = tid & 31;
+  const int nvalid = (int)(Ntot - g0 < kPos ? Ntot - g0 : kPos);     // positions of this tile inside the batch
+  const unsigned off0 = (unsigned)(((g0 + pos0) * O + col0 * 8) * 2);
+  __syncthreads();   // the input tile is in LDS (the DMA is drained in front of the barrier)
+
+#pragma unroll 1
+  for (int gi = 0; gi < NG; gi++) {
+    const int o0 = gi * 256;
+    s_bias[tid] = bias[o0 + tid];      // read behind the next barrier
+    // ---- main GEMM of this group
+    f32x4 acc[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; a++)
+#pragma unroll
+      for (int b = 0; b < 4; b++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) acc[a][b][r] = 0.f;
+    {
+      V w[2][4];
+      load_w16(wfrag, 0, G, gi * 4 + wave, 0, w[0]);
+#pragma unroll
+      for (int st = 0; st < 2 * CC; st++) {
+        if (st + 1 < 2 * CC) load_w16(wfrag, (st + 1) >> 1, G, gi * 4 + wave, (st + 1) & 1, w[(st + 1) & 1]);
+        mma16(s_x + (st >> 1) * kChunkB + pix16 * kRowBytes + bofs, 16 * kRowBytes, st & 1, w[st & 1], acc);
+        __builtin_amdgcn_sched_barrier(0);   // keep the later k-steps' loads from being hoisted (registers)
+      }
+    }
+    // residual vectors of the group's tile in flight under the staging
+    // (vector i of a thread: position pos0 + 8 i, 16-byte column col0 -- rows 8 positions = 8 * O * 2 bytes apart)
+    const unsigned offg = off0 + o0 * 2;
+    V r8[8];
+    if (has_res) {
+#pragma unroll
+      for (int i = 0; i < 8; i++)
+        r8[i] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(
+                                          rr, (int)(pos0 + 8 * i < nvalid ? offg + i * (8 * O * 2) : 0x80000000u), 0, 0));
+    }
+    __syncthreads();   // the previous group's chained GEMM has read the staged rows; s_bias is written
+#pragma unroll
+    for (int a = 0; a < 4; a++) {
+      const int och = wave * 64 + 16 * a + 4 * kg16;
+      const h4e bq = *reinterpret_cast<const h4e*>(s_bias + och);
+#pragma unroll
+      for (int b = 0; b < 4; b++) {
+        h2e lo = {(_Float16)(acc[a][b][0] + (float)bq[0]), (_Float16)(acc[a][b][1] + (float)bq[1])};
+        h2e hi = {(_Float16)(acc[a][b][2] + (float)bq[2]), (_Float16)(acc[a][b][3] + (float)bq[3])};
+        if (!has_res) {
+          lo = __builtin_elementwise_max(lo, h2e{(_Float16)0.f, (_Float16)0.f});
+          hi = __builtin_elementwise_max(hi, h2e{(_Float16)0.f, (_Float16)0.f});
+        }
+        *reinterpret_cast<h4e*>(s_st + (16 * b + pix16) * kStRowB + och * 2) = h4e{lo[0], lo[1], hi[0], hi[1]};
+      }
+    }
+    __syncthreads();
+    // chained filter fragments requested in front of the residual / store pass
+    V aw[C16 ? 4 : 16];
+    if constexpr (C16) {
+      load_w16(chain_w, gi * 4, G3, wave, 0, aw);
+    } else {
+      const V* cwp = reinterpret_cast<const V*>(chain_w) + lane + ((wave >> 1) * 8 + (wave & 1) * 4) * 64;
+#pragma unroll
+      for (int c4 = 0; c4 < 4; c4++)
+#pragma unroll
+        for (int kk = 0; kk < 4; kk++) aw[c4 * 4 + kk] = cwp[((int64_t)(gi * 4 + c4) * G3 * 8 + kk) * 64];
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      const int pos = pos0 + 8 * i, col = col0;
+      V v = *reinterpret_cast<const V*>(s_st + pos * kStRowB + col * 16);
+      if (has_res) {
+#pragma unroll
+        for (int e = 0; e < 8; e += 2) {
+          h2e p2 = {(_Float16)((float)v[e] + (float)r8[i][e]), (_Float16)((float)v[e + 1] + (float)r8[i][e + 1])};
+          p2 = __builtin_elementwise_max(p2, h2e{(_Float16)0.f, (_Float16)0.f});
+          v[e] = p2[0];
+          v[e + 1] = p2[1];
+        }
+        *reinterpret_cast<V*>(s_st + pos * kStRowB + col * 16) = v;   // finished rows back to LDS
+      }
+      if (pos < nvalid) *reinterpret_cast<V*>(reinterpret_cast<char*>(out) + (offg + i * (8 * O * 2))) = v;
+    }
+    __syncthreads();   // the finished 256-map rows of the tile are in LDS
+    // ---- this group's K-slice (channels o0 .. o0 + 255) of the chained GEMM
+    if constexpr (C16) {
+      V w2[4];
+#pragma unroll
+      for (int st = 0; st < NG3 * 8; st++) {       // (map group n, chunk c4, k-step): st = n * 8 + c4 * 2 + ks
+        constexpr int kLast = NG3 * 8 - 1;
+        const int nx = st + 1;
+        if (st < kLast) load_w16(chain_w, gi * 4 + ((nx >> 1) & 3), G3, wave + 4 * (nx >> 3), nx & 1, (st & 1) ? aw : w2);
+        mma16(s_st + pix16 * kStRowB + ((st >> 1) & 3) * 128 + bofs, 16 * kStRowB, st & 1, (st & 1) ? w2 : aw, cacc[st >> 3]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    } else {
+      // wave = 32 maps x 64 positions; K order (chunk, k-step) as the stand-alone OG = 2 launch
+#pragma unroll
+      for (int c4 = 0; c4 < 4; c4++)
+#pragma unroll
+        for (int kk = 0; kk < 4; kk++)
+#pragma unroll
+          for (int j = 0; j < 2; j++) {
+            const V bf = *reinterpret_cast<const V*>(s_st + (32 * j + (lane & 31)) * kStRowB + (c4 * 64 + kk * 16 + (lane >> 5) * 8) * 2);
+            c2[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aw[c4 * 4 + kk], bf, c2[j], 0, 0, 0);
+          }
+    }
+  }
+  __syncthreads();     // every wave is done with the input tile and the staged rows
+  // ---- chained result: bias + ReLU, rows staged (O3 * 2 + 16 bytes), whole rows stored 16 B per lane
+  constexpr int rowb = O3 * 2 + 16;
+  if constexpr (C16) {
+#pragma unroll
+    for (int n = 0; n < NG3; n++)
+#pragma unroll
+      for (int a = 0; a < 4; a++) {
+        const int och = (wave + 4 * n) * 64 + 16 * a + 4 * kg16;
+        const h4e bq = *reinterpret_cast<const h4e*>(chain_b + och);
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+          h2e lo = {(_Float16)(cacc[n][a][b][0] + (float)bq[0]), (_Float16)(cacc[n][a][b][1] + (float)bq[1])};
+          h2e hi = {(_Float16)(cacc[n][a][b][2] + (float)bq[2]), (_Float16)(cacc[n][a][b][3] + (float)bq[3])};
+          lo = __builtin_elementwise_max(lo, h2e{(_Float16)0.f, (_Float16)0.f});
+          hi = __builtin_elementwise_max(hi, h2e{(_Float16)0.f, (_Float16)0.f});
+          *reinterpret_cast<h4e*>(smem + (16 * b + pix16) * rowb + och * 2) = h4e{lo[0], lo[1], hi[0], hi[1]};
+        }
+      }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+#pragma unroll
+      for (int rq = 0; rq < 4; rq++) {
+        const int och = wave * 32 + 8 * rq + 4 * (lane >> 5);
+        const h4e bq = *reinterpret_cast<const h4e*>(chain_b + och);
+        h2e lo = {(_Float16)(c2[j][rq * 4] + (float)bq[0]), (_Float16)(c2[j][rq * 4 + 1] + (float)bq[1])};
+        h2e hi = {(_Float16)(c2[j][rq * 4 + 2] + (float)bq[2]), (_Float16)(c2[j][rq * 4 + 3] + (float)bq[3])};
+        lo = __builtin_elementwise_max(lo, h2e{(_Float16)0.f, (_Float16)0.f});
+        hi = __builtin_elementwise_max(hi, h2e{(_Float16)0.f, (_Float16)0.f});
+        *reinterpret_cast<h4e*>(smem + (32 * j + (lane & 31)) * rowb + och * 2) = h4e{lo[0], lo[1], hi[0], hi[1]};
+      }
+  }
+  __syncthreads();
+  constexpr int vpr = O3 / 8;
+#pragma unroll
+  for (int i = 0; i < kPos * vpr / 256; i++) {
+    const int idx = tid + 256 * i, pos = idx / vpr, col = idx % vpr;
+    if (g0 + pos < Ntot)
+      *reinterpret_cast<V*>(chain_out + (g0 + pos) * O3 + col * 8) = *reinterpret_cast<const V*>(smem + pos * rowb + col * 16);
+  }
+}
+
 // CU count of the CURRENT device (cached per device index: a process may drive devices of different size)
 inline int device_cu_count(int* out) {
   static int cached[64] = {};
@@ -2847,6 +3102,52 @@ extern "C" int s2a_conv3x3_tail1x1_f16(const void* x, const void* weight_frag, c
   return launch_conv<9, 1, 1, 1, true>((const _Float16*)x, (const _Float16*)weight_frag, (const _Float16*)bias, nullptr,
                                        (_Float16*)out, batch, 64, (int)height, (int)width, (int)height, (int)width, 1, 64,
                                        1, as_stream(stream), nullptr, 0, 0, ex);
+}
+
+namespace s2a {
+namespace {
+template <int CC, int O3>
+int launch_conv1x1_chain(const _Float16* x, const _Float16* wfrag, const _Float16* bias, const _Float16* residual, _Float16* out,
+                         const _Float16* cw, const _Float16* cb, _Float16* cout, int64_t P, hipStream_t st) {
+  constexpr int K = 64 * CC;
+  const int loop = CC * 64 * kRowBytes + 64 * 528 + 512;      // input tile + staged 256-map rows + bias
+  const int tail = 64 * (O3 * 2 + 16);                              // staged rows of the chained result (over the tile)
+  const int lds = loop > tail ? loop : tail;
+  auto kern = k_conv1x1_chain_f16<CC, O3>;
+  S2A_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  kern<<<dim3((unsigned)((P + 63) / 64)), 256, lds, st>>>(x, wfrag, bias, residual, out, cw, cb, cout, P,
+                                                          (unsigned)((uint64_t)P * K * 2));
+  S2A_LAUNCH_CHECK();
+  return S2A_OK;
+}
+}  // namespace
+}  // namespace s2a
+
+extern "C" int s2a_conv1x1_chain_f16(const void* x, const void* weight_frag, const void* bias, const void* residual,
+                                     void* out, const void* chain_weight_frag, const void* chain_bias, void* chain_out,
+                                     int64_t chain_channels, int64_t batch, int64_t channels, int64_t out_channels,
+                                     int64_t height, int64_t width, s2a_stream_t stream) {
+  S2A_CHECK_ARG(batch >= 0 && height > 0 && width > 0, "conv1x1_chain: bad shape");
+  S2A_CHECK_ARG((channels == 128 && out_channels == 512 && (chain_channels == 128 || chain_channels == 256)) ||
+                (channels == 256 && out_channels == 1024 && chain_channels == 256),
+                "conv1x1_chain: built for (K, O, O3) = (128, 512, 128), (128, 512, 256), (256, 1024, 256)");
+  S2A_CHECK_ARG((uint64_t)batch * height * width * out_channels * 2 < (1ull << 31),
+                "conv1x1_chain: tensor too large for 32-bit offsets");
+  S2A_CHECK_ARG((chain_weight_frag && chain_bias && chain_out) || (!chain_weight_frag && !chain_bias && !chain_out),
+                "conv1x1_chain: chain filter, bias and output go together");
+  if (batch == 0) return S2A_OK;
+  S2A_CHECK_ARG(x && weight_frag && bias && out && chain_weight_frag, "conv1x1_chain: NULL tensor");
+  S2A_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)weight_frag % 16) == 0 &&
+                ((uintptr_t)bias % 8) == 0 && ((uintptr_t)residual % 16) == 0 && ((uintptr_t)chain_weight_frag % 16) == 0 &&
+                ((uintptr_t)chain_bias % 8) == 0 && ((uintptr_t)chain_out % 16) == 0,
+                "conv1x1_chain: tensors must be 16-byte aligned");
+  const int64_t P = batch * height * width;
+  const _Float16 *X = (const _Float16*)x, *Wf = (const _Float16*)weight_frag, *Bi = (const _Float16*)bias,
+                 *R = (const _Float16*)residual, *Cw = (const _Float16*)chain_weight_frag, *Cb = (const _Float16*)chain_bias;
+  hipStream_t st = as_stream(stream);
+  if (channels == 256) return launch_conv1x1_chain<4, 256>(X, Wf, Bi, R, (_Float16*)out, Cw, Cb, (_Float16*)chain_out, P, st);
+  if (chain_channels == 128) return launch_conv1x1_chain<2, 128>(X, Wf, Bi, R, (_Float16*)out, Cw, Cb, (_Float16*)chain_out, P, st);
+  return launch_conv1x1_chain<2, 256>(X, Wf, Bi, R, (_Float16*)out, Cw, Cb, (_Float16*)chain_out, P, st);
 }
 
 extern "C" int s2a_conv1x1_add_up2_f16(const void* x, const void* weight_frag, const void* bias, const void* coarse,

@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .fused import FusedConv2d, bottleneck_chain_ok, bottleneck_tail, bottleneck_tail_ok
+from .fused import Conv3Chain, FusedConv2d, bottleneck_chain_ok, bottleneck_tail, bottleneck_tail_ok, conv3_chain_ok
 from .head import S2ANetHead
 
 
@@ -40,7 +40,7 @@ class BottleNeck(nn.Module):
 
     def forward_chain(self, x, pre=None, nxt=None):
         """-> (block output, the NEXT block's conv1 output or None).  pre = this block's conv1 output when the previous
-        block's tail kernel already produced it; nxt = the next block (run_blocks)."""
+        block's tail or conv3 launch already produced it; nxt = the next block (run_blocks)."""
         residual = x
         if isinstance(self.conv3, FusedConv2d):           # BN folded, epilogues fused (inference)
             out = pre if pre is not None else self.conv1(x)
@@ -50,6 +50,10 @@ class BottleNeck(nn.Module):
                 if isinstance(nxt, BottleNeck) and bottleneck_chain_ok(nxt.conv1):
                     return bottleneck_tail(out, self.conv2, self.conv3, residual, nxt.conv1)
                 return bottleneck_tail(out, self.conv2, self.conv3, residual), None
+            if isinstance(nxt, BottleNeck) and conv3_chain_ok(self.conv3, nxt.conv1):
+                # conv3 + residual + ReLU and the next block's conv1 in one launch (stages 2 and 3, and into layer3.0)
+                ch = Conv3Chain(nxt.conv1)
+                return self.conv3(self.conv2(out), residual, chain=ch), ch.out
             return self.conv3(self.conv2(out), residual), None  # relu(conv3 + bias + residual) in one pass
         return self._forward_plain(x), None
 

@@ -122,9 +122,12 @@ def conv_wino_f16(x, packed_wino, bias, out_channels, relu=False, pool=False):
     return r.view(B, H, W, out_channels).permute(0, 3, 1, 2)
 
 
-def conv_f16(x, packed_weight, bias, out_channels, ksize, stride=1, relu=False, residual=None, out=None):
+def conv_f16(x, packed_weight, bias, out_channels, ksize, stride=1, relu=False, residual=None, out=None, chain=None):
     """relu?(conv(x) + bias (+ residual)) in ONE kernel; x f16 channels-last, packed_weight from
-    conv_pack_weight; ksize 3 (pad 1, stride 1|2) or 1 (pad 0, stride 1|2)"""
+    conv_pack_weight; ksize 3 (pad 1, stride 1|2) or 1 (pad 0, stride 1|2).
+    chain = a Conv3Chain (this launch is a bottleneck's conv3, chain.conv the next block's conv1, conv3_chain_ok):
+    the same launch also leaves relu(conv1(result)) in chain.out (s2a_conv1x1_chain_f16); the return value is the same
+    tensor, bit for bit, as without it"""
     B, C, H, W = x.shape
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     O_real = out_channels
@@ -143,11 +146,48 @@ def conv_f16(x, packed_weight, bias, out_channels, ksize, stride=1, relu=False, 
     if residual is not None:
         assert residual.shape == out.shape and residual.dtype == torch.float16 and \
             residual.is_contiguous(memory_format=torch.channels_last)
+    if chain is not None and ksize == 1 and stride == 1 and relu and b is not None and \
+            (C, out_channels, chain.conv.out_channels) in CONV3_CHAIN_SHAPES and out.numel() * 2 < (1 << 31):
+        wc, bc, _ = chain.conv.packed_args()
+        chain.out = torch.empty((B, chain.conv.out_channels, H, W), dtype=torch.float16, device=x.device,
+                                memory_format=torch.channels_last)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().s2a_conv1x1_chain_f16(_lib.ptr(x), _lib.ptr(packed_weight), _lib.ptr(b), _lib.ptr(residual),
+                                                        _lib.ptr(out), _lib.ptr(wc), _lib.ptr(bc), _lib.ptr(chain.out),
+                                                        chain.conv.out_channels, B, C, out_channels, H, W,
+                                                        _lib.stream_ptr(x.device)))
+        return out
     with torch.cuda.device(x.device):
         _lib.check(_lib.lib().s2a_conv_nhwc_f16(_lib.ptr(x), _lib.ptr(packed_weight), _lib.ptr(b), _lib.ptr(residual),
                                                 _lib.ptr(out), B, C, H, W, out_channels, int(ksize), int(stride),
                                                 int(bool(relu)), _lib.stream_ptr(x.device)))
     return out if O_real == out_channels else out[:, :O_real]
+
+
+# (conv3 in, conv3 out, next conv1 out) the chained kernel is built for: layer2's blocks, layer2 -> layer3.0, layer3's
+# blocks.  (256, 1024, 512), layer3 -> layer4.0, does not fit the register file without scratch (docs/HISTORY.md)
+CONV3_CHAIN_SHAPES = {(128, 512, 128), (128, 512, 256), (256, 1024, 256)}
+
+
+class Conv3Chain:
+    """the next bottleneck's conv1 riding on a conv3 launch: conv = that FusedConv2d; out = its result, filled by
+    conv_f16 when the launch really chained it (None otherwise: the caller runs conv1 itself)"""
+
+    def __init__(self, conv):
+        self.conv, self.out = conv, None
+
+
+def conv3_chain_ok(conv3, conv1):
+    """the next block's conv1 can ride on this block's conv3 launch (s2a_conv1x1_chain_f16): both 1x1 / stride 1 with
+    bias and ReLU, f16, conv1 reading what conv3 writes, a (K, O, O3) the kernel is built for, inference only"""
+    import os
+    def plain(c):
+        return (isinstance(c, FusedConv2d) and tuple(c.kernel_size) == (1, 1) and tuple(c.stride) == (1, 1) and
+                tuple(c.padding) == (0, 0) and tuple(c.dilation) == (1, 1) and c.groups == 1 and c.bias is not None and
+                c.fuse_relu and c.weight.dtype == torch.float16)
+    return (not torch.is_grad_enabled() and not os.environ.get("S2A_NO_CONV3_CHAIN") and plain(conv3) and plain(conv1) and
+            conv1.in_channels == conv3.out_channels and
+            (conv3.in_channels, conv3.out_channels, conv1.out_channels) in CONV3_CHAIN_SHAPES)
 
 
 def bottleneck_tail_ok(x, conv2, conv3, residual):
@@ -319,8 +359,9 @@ class FusedConv2d(nn.Conv2d):
             self._packed = PackedWeightCache()
         return self._packed.get_wino(self.weight), self._packed.get_bias(self.bias, self.out_channels), self.out_channels
 
-    def forward(self, x, residual=None, out=None):
-        """out: dense NHWC buffer for the result (library path only; the own kernel is called with out= directly)"""
+    def forward(self, x, residual=None, out=None, chain=None):
+        """out: dense NHWC buffer for the result (library path only; the own kernel is called with out= directly);
+        chain: a Conv3Chain, honoured on the own-kernel path only (conv_f16)"""
         if out is not None:
             assert x.is_cuda and self.bias is not None and not torch.is_grad_enabled() and not own_conv_ok(
                 x, self.in_channels, self.out_channels, self.kernel_size, self.stride, self.padding, self.dilation, self.groups)
@@ -332,8 +373,9 @@ class FusedConv2d(nn.Conv2d):
                     residual.dtype == torch.float16 and residual.is_contiguous(memory_format=torch.channels_last))):
             if not hasattr(self, "_packed"):
                 self._packed = PackedWeightCache()
+            kw = {} if chain is None else {"chain": chain}
             return conv_f16(x, self._packed.get(self.weight), self._packed.get_bias(self.bias, max(64, self.out_channels)),
-                            self.out_channels, self.kernel_size[0], self.stride[0], self.fuse_relu, residual)
+                            self.out_channels, self.kernel_size[0], self.stride[0], self.fuse_relu, residual, **kw)
         if (not x.is_cuda) or self.bias is None:
             y = super().forward(x)
             if residual is not None:
