@@ -737,6 +737,76 @@ typedef struct s2a_loss_grad_map {
 int s2a_s2anet_loss_backward(const s2a_loss_grad_map* maps, int n_maps, const float* grad_loss, const float* norm,
                              s2a_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Training update: the end of the reference's iteration (train.py:358-373, utils/torch_utils.py:276-307) as one
+ * capturable launch sequence -- GradScaler.unscale_, clip_grad_norm_, scaler.step(SGD with momentum / Nesterov and
+ * parameter groups), scaler.update, zero_grad (to zero, not to None) and ModelEMA.update.
+ *
+ * All tensors are contiguous f32 and are described by two DEVICE tables that the caller builds once:
+ *   tensors  one s2a_optim_tensor per tensor.  kind S2A_OPTIM_TRAINED: p, grad, momentum_buf are updated, ema too unless
+ *            it is NULL; kind S2A_OPTIM_EMA_ONLY: ema follows p (a floating buffer or a frozen parameter), grad and
+ *            momentum_buf are not read.  group indexes lr / hyper.
+ *   chunks   int64 [n_chunks, 2] = (tensor, first element): chunk c covers elements [start, min(start +
+ *            S2A_OPTIM_CHUNK, numel)) of its tensor; start is a multiple of S2A_OPTIM_CHUNK.  The chunks of the trained
+ *            tensors come first (n_trained_chunks of them), in tensor order, so the norm is summed in a fixed order.
+ * lr f32 [n_groups]; hyper f32 [n_groups, 4] = (momentum, weight_decay, nesterov != 0, reserved); both on the device.
+ *
+ * Launches (on `stream`, geometry from the host arguments only; no host read, allocation, memset node or float atomic):
+ *   1  partials   per trained chunk: f32 sum of (grad / scale)^2, reduced per workgroup in a fixed order, and a flag from
+ *                 a per-element isfinite test of grad.  Skipped when neither max_norm nor scaling is enabled.
+ *   2  finalise   one workgroup: partials added in chunk order in double; total_norm = sqrt; clip = min(1, max_norm /
+ *                 (total_norm + 1e-6)) (1 when max_norm <= 0; a NaN norm gives a NaN clip as torch's clamp does);
+ *                 found_inf = OR of the flags; skip_update = (scaling enabled && found_inf) || *skip != 0; the scale
+ *                 follows torch's _amp_update_scale_ on found_inf alone (x backoff and tracker 0, else ++tracker and
+ *                 x growth when it reaches growth_interval and the product is finite); updates += 1 and
+ *                 d = ema_decay * (1 - exp(-updates / ema_tau)) in double.
+ *   3  apply      per element, skip_update == 0: g = grad / scale * clip; g += wd * p when wd != 0;
+ *                 buf = momentum * buf + g; g = nesterov ? g + momentum * buf : buf; p -= lr * g.  skip_update == 1: p and
+ *                 buf are not written.  Always: ema = d * ema + (1 - d) * p with the new p, and grad = 0.
+ * scale f32 [1] and counters int32 [2] = (growth_tracker, updates) are device state, read and written; scale is neither
+ * read nor written when scaling_enabled == 0.  skip: optional device flag, int32 (skip_elem_bytes 4) or int64 (8).
+ * stats f32 [S2A_OPTIM_STATS] = (unscaled pre-clip gradient norm (0 when launch 1 is skipped), clip, found_inf,
+ * skip_update, new scale, d, updates, growth_tracker).
+ * Rows whose four pointers are all 16-byte aligned are walked with 16-byte accesses, others and tails element-wise.
+ * workspace: s2a_train_update_workspace_bytes(n_trained_chunks), 16-byte aligned. */
+#define S2A_OPTIM_CHUNK 4096
+#define S2A_OPTIM_STATS 8
+#define S2A_OPTIM_TRAINED 0
+#define S2A_OPTIM_EMA_ONLY 1
+
+typedef struct s2a_optim_tensor {
+  float* p;
+  float* grad;
+  float* momentum_buf;
+  float* ema;
+  int64_t numel;
+  int32_t group;
+  int32_t kind;
+} s2a_optim_tensor;
+
+typedef struct s2a_train_update_args {
+  const s2a_optim_tensor* tensors; /* device */
+  const int64_t* chunks;           /* device */
+  int64_t n_tensors, n_chunks, n_trained_chunks;
+  const float* lr;                 /* device */
+  const float* hyper;              /* device */
+  int32_t n_groups;
+  int32_t scaling_enabled;
+  float* scale;                    /* device */
+  int32_t* counters;               /* device */
+  const void* skip;                /* device or NULL */
+  int32_t skip_elem_bytes;
+  int32_t growth_interval;
+  float max_norm;                  /* <= 0: no clipping */
+  float growth_factor, backoff_factor;
+  float reserved;
+  double ema_decay, ema_tau;
+  float* stats;                    /* device */
+} s2a_train_update_args;
+
+size_t s2a_train_update_workspace_bytes(int64_t n_trained_chunks);
+int s2a_train_update(const s2a_train_update_args* args, void* workspace, size_t workspace_bytes, s2a_stream_t stream);
+
 /* 0 for a normal build; non-zero when an object was compiled with a measurement / ablation switch (-DS2A_MEASURE,
  * -DS2A_ABL=..., -DS2A_STAMP=1: such a build may skip work or print diagnostics). */
 int s2a_build_flags(void);

@@ -15,6 +15,7 @@ from .loss import S2ANetLossFunction, s2anet_loss, grid_anchors
 from .fused import drop_weight_caches
 from .scene import tile_grid, chip_names, gather_chips, merge_detections, SceneDetections
 from .evaluate import evaluate_task1, Task1Evaluator, Task1Result, claim_tp_fp
+from .optim import TrainUpdate, reference_param_groups, reference_lr
 
 __all__ = [
     "box_iou_rotated", "nms_rotated", "ml_nms_rotated", "multiclass_nms_rotated",
@@ -24,4 +25,5 @@ __all__ = [
     "rot_inv_pool_backward", "S2ANetLossFunction", "s2anet_loss", "grid_anchors", "drop_weight_caches",
     "tile_grid", "chip_names", "gather_chips", "merge_detections", "SceneDetections",
     "evaluate_task1", "Task1Evaluator", "Task1Result", "claim_tp_fp",
+    "TrainUpdate", "reference_param_groups", "reference_lr",
 ]

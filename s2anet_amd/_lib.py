@@ -70,6 +70,25 @@ class EvalCurves(ctypes.Structure):
                 ("prec", c_vp), ("seg_start", c_vp)]
 
 
+class OptimTensor(ctypes.Structure):
+    """s2a_optim_tensor: one row of the training update's device tensor table"""
+    _fields_ = [("p", c_vp), ("grad", c_vp), ("momentum_buf", c_vp), ("ema", c_vp), ("numel", c_i64),
+                ("group", ctypes.c_int32), ("kind", ctypes.c_int32)]
+
+
+class TrainUpdateArgs(ctypes.Structure):
+    """s2a_train_update_args"""
+    _fields_ = [("tensors", c_vp), ("chunks", c_vp), ("n_tensors", c_i64), ("n_chunks", c_i64), ("n_trained_chunks", c_i64),
+                ("lr", c_vp), ("hyper", c_vp), ("n_groups", ctypes.c_int32), ("scaling_enabled", ctypes.c_int32),
+                ("scale", c_vp), ("counters", c_vp), ("skip", c_vp), ("skip_elem_bytes", ctypes.c_int32),
+                ("growth_interval", ctypes.c_int32), ("max_norm", c_f32), ("growth_factor", c_f32),
+                ("backoff_factor", c_f32), ("reserved", c_f32), ("ema_decay", ctypes.c_double), ("ema_tau", ctypes.c_double),
+                ("stats", c_vp)]
+
+
+OPTIM_CHUNK, OPTIM_STATS, OPTIM_TRAINED, OPTIM_EMA_ONLY = 4096, 8, 0, 1
+
+
 class AnchorSet(ctypes.Structure):
     """s2a_anchor_set: one anchor set of s2a_assign_labels_batched"""
     _fields_ = [("anchors", c_vp), ("batch_stride", c_i64)]
@@ -185,6 +204,8 @@ SYMBOLS = {
     "s2a_eval_task1": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_int32, ctypes.c_int32,
                                ctypes.c_double, c_int, c_int, ctypes.POINTER(ctypes.c_double)] + [c_vp] * 9 +
                        [ctypes.POINTER(EvalCurves), c_vp, c_sz, c_vp]),
+    "s2a_train_update_workspace_bytes": (c_sz, [c_i64]),
+    "s2a_train_update": (c_int, [ctypes.POINTER(TrainUpdateArgs), c_vp, c_sz, c_vp]),
     "s2a_delta2bbox_rotated": (c_int, [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp]),
     "s2a_fam_refine_anchors": (c_int, [c_vp, c_i64, c_i64, c_i64, c_f32, c_f32, c_int, c_int,
                                        c_vp, c_vp]),
