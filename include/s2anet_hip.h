@@ -487,6 +487,33 @@ int s2a_conv_nhwc_f16(const void* x, const void* weight_frag, const void* bias, 
                       void* out, int64_t batch, int64_t channels, int64_t height, int64_t width,
                       int64_t out_channels, int ksize, int stride, int relu, s2a_stream_t stream);
 
+/* Training side of the regular convolutions above (FusedConv2d with own_grad; stride 1, ksize 3 / pad 1 or ksize 1 / pad 0,
+ * C and O multiples of 64, every tensor under 2^31 bytes).  All three are fixed launch sequences without host reads, float
+ * atomics or memset nodes: capturable, and bit-identical from call to call.
+ * s2a_conv_pack_weight_train: the master filter [O,C,k,k] (contiguous, weight_dtype F32 or F16) -> two f16 filters in the
+ *   order of s2a_conv_pack_weight_f16, in one launch: packed_fwd (the filter itself) and, unless NULL, packed_dgrad, the
+ *   input-gradient filter w'[c,o,ky,kx] = w[o,c,k-1-ky,k-1-kx] (a [C,O,k,k] filter: s2a_conv_nhwc_f16 on the output gradient
+ *   with it, channels = O, out_channels = C, gives the input gradient).
+ * s2a_conv_backward_prep_f16: one pass over grad_out [positions, O] f16.  out (the forward's ReLU output, or NULL when no
+ *   ReLU was fused): g = grad_out * (out > 0), written to g unless g is NULL.  grad_bias [O] (grad_bias_dtype, or NULL): the
+ *   per-channel sums of g (of grad_out without out), f32 partials per workgroup summed in workgroup order.  With neither g
+ *   nor grad_bias nothing is launched.  workspace: only for grad_bias.
+ * s2a_conv_backward_weight_f16: grad_weight[o,c,ky,kx] (grad_dtype, contiguous [O,C,k,k]) =
+ *   sum over (b,y,x) of g[b,y,x,o] * x[b,y+ky-pad,x+kx-pad,c], zero padding, f32 accumulation; x [B,H,W,C], g [B,H,W,O] f16.
+ *   Split over position slices into per-slice f32 partials that a second launch sums in slice order; the split depends on
+ *   the shapes only. */
+int s2a_conv_pack_weight_train(const void* weight, int weight_dtype, int64_t out_channels, int64_t channels, int ksize,
+                               void* packed_fwd, void* packed_dgrad, s2a_stream_t stream);
+size_t s2a_conv_backward_prep_f16_workspace_bytes(int64_t positions, int64_t out_channels);
+int s2a_conv_backward_prep_f16(const void* grad_out, const void* out, void* g, void* grad_bias, int grad_bias_dtype,
+                               int64_t positions, int64_t out_channels, void* workspace, size_t workspace_bytes,
+                               s2a_stream_t stream);
+size_t s2a_conv_backward_weight_f16_workspace_bytes(int64_t batch, int64_t channels, int64_t height, int64_t width,
+                                                    int64_t out_channels, int ksize);
+int s2a_conv_backward_weight_f16(const void* x, const void* g, void* grad_weight, int grad_dtype, int64_t batch,
+                                 int64_t channels, int64_t height, int64_t width, int64_t out_channels, int ksize,
+                                 void* workspace, size_t workspace_bytes, s2a_stream_t stream);
+
 /* Training side of the deformable convolution: the three device functions the reference's
  * backward is composed of (models/dcn/src/deform_conv_cuda_kernel.cu): deformable_im2col (:244-276),
  * deformable_col2im (:332-370), deformable_col2im_coord (:431-464).  p->batch = the number of images of

@@ -324,8 +324,102 @@ def drop_weight_caches(module):
     return module
 
 
+def train_conv_ok(x, conv, residual=None):
+    """limits of the own training route (FusedConvFunction), and nothing but limits: f16 channels-last activations on the
+    GPU, stride 1, 3x3 / pad 1 or 1x1 / pad 0, channel counts multiples of 64, f16 or f32 parameters, a residual of the
+    output's shape and layout, input and output under 2^31 bytes.  The speed heuristics of own_conv_ok play no part:
+    a layer on this route is bit-reproducible whatever its size."""
+    if not (x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 and x.numel() > 0 and
+            x.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    k, pd = tuple(conv.kernel_size), tuple(conv.padding)
+    if not (tuple(conv.dilation) == (1, 1) and conv.groups == 1 and tuple(conv.stride) == (1, 1) and
+            ((k == (3, 3) and pd == (1, 1)) or (k == (1, 1) and pd == (0, 0))) and
+            conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0 and x.shape[1] == conv.in_channels):
+        return False
+    w, b = conv.weight, conv.bias
+    if w.dtype not in (torch.float16, torch.float32) or not w.is_cuda or (b is not None and b.dtype != w.dtype):
+        return False
+    B, _, H, W = x.shape
+    if residual is not None and not (residual.is_cuda and residual.dtype == torch.float16 and
+                                     tuple(residual.shape) == (B, conv.out_channels, H, W) and
+                                     residual.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    return x.numel() * 2 < (1 << 31) and B * H * W * conv.out_channels * 2 < (1 << 31)
+
+
+def train_kernels(module, enabled=True):
+    """own_grad = enabled on every FusedConv2d of the tree -> how many were set.  With own_grad a grad-enabled forward of
+    an eligible layer (train_conv_ok) runs FusedConvFunction: forward, input gradient, weight gradient, bias gradient and
+    ReLU mask on the project's kernels.  Every other layer and every other call keeps its route."""
+    n = 0
+    for m in module.modules():
+        if isinstance(m, FusedConv2d):
+            m.own_grad = bool(enabled)
+            n += 1
+    return n
+
+
+class FusedConvFunction(torch.autograd.Function):
+    """relu?(conv(x) + bias (+ residual)) with its backward on the own kernels.  x f16 channels-last; weight / bias f16
+    or f32 (masters: rounded to f16 by the pack, gradients straight from the f32 sums); stride 1, 3x3 / pad 1 or 1x1.
+    The filter is packed on EVERY call (s2a_conv_pack_weight_train: forward order and input-gradient order in one
+    launch), never cached: weights change every step, and a graph replay moves no version counter.  No host read,
+    launch geometry from shapes only, workspaces from the torch allocator: forward + backward can be captured."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, relu):
+        O, C, k, _ = weight.shape
+        L = _lib.lib()
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        w = weight.detach()
+        w = w if w.is_contiguous() else w.contiguous()            # (a channels-last 3x3 filter: one stock copy)
+        fwd = torch.empty((w.numel(),), dtype=torch.float16, device=x.device)
+        dgrad = torch.empty_like(fwd) if need_x else None
+        with torch.cuda.device(x.device):
+            _lib.check(L.s2a_conv_pack_weight_train(_lib.ptr(w), _lib.dtype_code(w), O, C, k, _lib.ptr(fwd), _lib.ptr(dgrad),
+                                                    _lib.stream_ptr(x.device)))
+        out = conv_f16(x, fwd, None if bias is None else bias.detach(), O, k, 1, relu, residual)
+        ctx.save_for_backward(x if need_w else None, out if relu else None, dgrad)
+        ctx.geom = (tuple(x.shape), O, k, weight.dtype, None if bias is None else bias.dtype)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, out, dgrad = ctx.saved_tensors
+        (B, C, H, W), O, k, wdtype, bdtype = ctx.geom
+        need_x, need_w, need_b, need_r = ctx.needs_input_grad[:4]
+        L, dev = _lib.lib(), grad_out.device
+        go = grad_out if grad_out.dtype == torch.float16 else grad_out.to(torch.float16)
+        go = go.contiguous(memory_format=torch.channels_last)
+        st = _lib.stream_ptr(dev)
+        g, gb = go, None
+        need_g = need_x or need_w or need_r
+        with torch.cuda.device(dev):
+            if (out is not None and need_g) or need_b:
+                if out is not None and need_g:
+                    g = torch.empty_like(go)
+                ws = None
+                if need_b:
+                    gb = torch.empty((O,), dtype=bdtype, device=dev)
+                    ws = torch.empty((L.s2a_conv_backward_prep_f16_workspace_bytes(B * H * W, O),), dtype=torch.uint8, device=dev)
+                _lib.check(L.s2a_conv_backward_prep_f16(_lib.ptr(go), _lib.ptr(out), _lib.ptr(g if g is not go else None),
+                                                        _lib.ptr(gb), 0 if gb is None else _lib.dtype_code(gb), B * H * W, O,
+                                                        _lib.ptr(ws), 0 if ws is None else ws.numel(), st))
+            gx = conv_f16(g, dgrad, None, C, k, 1, False) if need_x else None
+            gw = None
+            if need_w:
+                gw = torch.empty((O, C, k, k), dtype=wdtype, device=dev)
+                ws = torch.empty((L.s2a_conv_backward_weight_f16_workspace_bytes(B, C, H, W, O, k),), dtype=torch.uint8, device=dev)
+                _lib.check(L.s2a_conv_backward_weight_f16(_lib.ptr(x), _lib.ptr(g), _lib.ptr(gw), _lib.dtype_code(gw), B, C, H, W,
+                                                          O, k, _lib.ptr(ws), ws.numel(), st))
+        return gx, gw, gb, (g if need_r else None), None
+
+
 class FusedConv2d(nn.Conv2d):
     """nn.Conv2d + (bias, optional residual, optional ReLU) epilogue in one pass"""
+    own_grad = False        # train_kernels(): grad-enabled forwards of eligible layers (train_conv_ok) run FusedConvFunction
 
     def __init__(self, *args, relu=False, **kw):
         super().__init__(*args, **kw)
@@ -362,6 +456,9 @@ class FusedConv2d(nn.Conv2d):
     def forward(self, x, residual=None, out=None, chain=None):
         """out: dense NHWC buffer for the result (library path only; the own kernel is called with out= directly);
         chain: a Conv3Chain, honoured on the own-kernel path only (conv_f16)"""
+        if out is None and self.own_grad and _needs_grad(x, self.weight, self.bias, residual) and \
+                train_conv_ok(x, self, residual):
+            return FusedConvFunction.apply(x, self.weight, self.bias, residual, self.fuse_relu)   # (chain= is ignored, as under grad)
         if out is not None:
             assert x.is_cuda and self.bias is not None and not torch.is_grad_enabled() and not own_conv_ok(
                 x, self.in_channels, self.out_channels, self.kernel_size, self.stride, self.padding, self.dilation, self.groups)
