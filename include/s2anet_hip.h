@@ -835,7 +835,8 @@ size_t s2a_train_update_workspace_bytes(int64_t n_trained_chunks);
 int s2a_train_update(const s2a_train_update_args* args, void* workspace, size_t workspace_bytes, s2a_stream_t stream);
 
 /* 0 for a normal build; non-zero when an object was compiled with a measurement / ablation switch (-DS2A_MEASURE,
- * -DS2A_ABL=..., -DS2A_STAMP=1: such a build may skip work or print diagnostics). */
+ * -DS2A_WABL=..., -DS2A_STAMP=1: such a build may skip work or print diagnostics).  Bits 0-7 (the former AlignConv
+ * ablation mask) are no longer set by any object. */
 int s2a_build_flags(void);
 
 /* Diagnostic builds only (-DS2A_STAMP=1): per-workgroup s_memtime phase stamps of the AlignConv

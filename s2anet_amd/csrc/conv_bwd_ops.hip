@@ -13,7 +13,7 @@ using s16x4b = __attribute__((ext_vector_type(4))) short;
 using s16x8b = __attribute__((ext_vector_type(8))) short;
 
 // ================================================================= filter pack (every step: the masters change)
-// fragment order of k_pack_weight_frag (dcn_ops.hip): [stage = cc*taps+t][och group of 64][mt 2][kk 4][lane 64][8 halfs],
+// fragment order of k_pack_weight_frag (conv_ops.hip): [stage = cc*taps+t][och group of 64][mt 2][kk 4][lane 64][8 halfs],
 // lane l, element j of fragment (mt,kk) = W[g*64 + mt*32 + (l&31)][cc*64 + kk*16 + 8*(l>>5) + j][t]
 __device__ __forceinline__ void frag_coords(int64_t e, int O, int taps, int& och, int& k, int& t) {
   const int G = O / 64;

@@ -2,7 +2,7 @@
 //
 // Serves the regular 256 -> 256 convolutions of S2ANetHead (models/head.py:163-222: fam_reg_ls, fam_cls_ls, odm_reg_ls,
 // odm_cls_ls, or_conv; forward_single :296-348), where the reference calls cuDNN (which picks its own algorithm; the
-// arithmetic type stays f16 in / f32 accumulate).  The direct kernel (dcn_ops.hip: k_conv_f16) spends 9 C O multiply-adds
+// arithmetic type stays f16 in / f32 accumulate).  The direct kernel (conv_ops.hip: k_conv_f16) spends 9 C O multiply-adds
 // per output; this one 6 C O:
 //     d0..d3 = four neighbouring pixels of an input row (columns 2t-1 .. 2t+2)
 //     V0 = d0 - d2, V1 = d1 + d2, V2 = d2 - d1, V3 = d1 - d3                               (input transform, f16)

@@ -16,7 +16,13 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ["s2anet_amd/csrc/dcn_ops.hip", "s2anet_amd/csrc/common.hpp"]      # k_dcn_patch and k_conv_f16 live here
+_SHARED = ["s2anet_amd/csrc/mfma_common.hpp", "s2anet_amd/csrc/common.hpp"]
+# record key -> (the kernel whose dispatches it averages, the files that kernel is compiled from): an edit of one kernel's
+# translation unit leaves the other kernel's record valid
+KEYS = {
+    "align_conv_pyramid": ("k_dcn_patch", ["s2anet_amd/csrc/dcn_ops.hip"] + _SHARED),
+    "conv_tower_pyramid": ("k_conv_f16", ["s2anet_amd/csrc/conv_ops.hip"] + _SHARED),
+}
 
 
 def collect(root, pat):
@@ -46,6 +52,8 @@ def main():
     for spec in sys.argv[4:]:
         key, rest = spec.split("=", 1)
         parts = rest.split(",")
+        kernel, sources = KEYS[key]
+        assert kernel in parts[0], f"{key} is the record of {kernel}, not of {parts[0]}"
         agg = collect(root, parts[0])
         if not agg.get("FETCH_SIZE") or not agg.get("WRITE_SIZE"):
             print("no FETCH_SIZE / WRITE_SIZE dispatches for", parts[0], file=sys.stderr)
@@ -55,7 +63,7 @@ def main():
         rec["kernels"][key] = {"kernel": parts[0], "fetch_kib": round(fk, 1), "write_kib": round(wk, 1),
                                "bytes": round((2 * fk + wk) * 1024), "dispatches": len(agg["FETCH_SIZE"]),
                                "batch": int(parts[1]), "pixels": int(parts[2]),
-                               "sources": SOURCES, "source_sha16": sha16(SOURCES)}
+                               "sources": sources, "source_sha16": sha16(sources)}
     rec["command"] = "rocprofv3 --kernel-trace --pmc <FETCH_SIZE | WRITE_SIZE> -- python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline"
     rec["git_head"] = os.environ.get("S2A_GIT_HEAD")       # filled in when the record is copied into profiles/ (no .git on the GPU box)
     json.dump(rec, open(out, "w"), indent=1)

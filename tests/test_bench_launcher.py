@@ -1,9 +1,11 @@
 """CPU: `python bench.py --gpus 2` from a bare shell launches its own ranks (bench.py:launch_ranks) and runs the
 multi-rank step loop end to end — process-group bring-up, barrier-bracketed timing, the DetectionGather slots, the
 overflow accumulator, ONE JSON line from rank 0 — on gloo with the detector stubbed (S2A_BENCH_STUB=1: no GPU here).
-Also: the traffic record bench.py reports is dropped as stale when the kernel sources changed."""
+Also: the traffic record bench.py reports is dropped as stale when the kernel sources changed, and every record
+scripts/pmc_summary.py writes hashes the files its kernel is compiled from."""
 import json
 import os
+import re
 import subprocess
 import sys
 
@@ -126,3 +128,19 @@ def test_recorded_traffic_goes_stale_with_the_sources(tmp_path, monkeypatch):
     assert bench.recorded_traffic("align_conv_pyramid", 8, 174592) == (None, True)
     monkeypatch.setattr(bench, "traffic_json", lambda: None)
     assert bench.recorded_traffic("align_conv_pyramid", 8, 174592) == (None, True)
+
+
+def test_traffic_record_sources_hold_the_kernel():
+    """a record that hashes the wrong file can never go stale: for every key scripts/pmc_summary.py can emit, every
+    listed source exists and one of them defines the key's kernel"""
+    sys.path.insert(0, os.path.join(ROOT, "scripts"))
+    import pmc_summary
+    assert set(pmc_summary.KEYS) == {"align_conv_pyramid", "conv_tower_pyramid"}
+    assert pmc_summary.KEYS["align_conv_pyramid"][0] == "k_dcn_patch" and pmc_summary.KEYS["conv_tower_pyramid"][0] == "k_conv_f16"
+    for key, (kernel, sources) in pmc_summary.KEYS.items():
+        text = ""
+        for p in sources:
+            assert os.path.isfile(os.path.join(ROOT, p)), (key, p)
+            with open(os.path.join(ROOT, p)) as f:
+                text += f.read()
+        assert re.search(r"__global__[^;{]*\b" + kernel + r"\(", text), (key, kernel)

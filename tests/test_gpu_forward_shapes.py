@@ -53,8 +53,8 @@ def tau(kind, K):
     K products per output):
     conv      exact f16 products summed in f32 (K v), + bias in f32, ONE f16 rounding, ReLU on the rounded value
                                                                                    -> u + (K + 17) v
-    conv_res  rnd16(rnd16(acc + b) + r): the residual / up-2 coarse epilogue rounds twice (dcn_ops.hip:1951, the tail
-              kernel :1856)                                                       -> 2u + (K + 17) v
+    conv_res  rnd16(rnd16(acc + b) + r): the residual / up-2 coarse epilogue rounds twice (k_conv_f16: its residual pass
+              and its fused tail)                                                     -> 2u + (K + 17) v
     stem      as conv (K = 147; the zero-padded K steps add nothing), ReLU and the max-pool exact, through the pooled S
                                                                                    -> u + (K + 17) v
     dcn16     f16 bilinear weights (u), one product and three FMAs in packed half (4u, blend_pk), exact f16 products

@@ -998,8 +998,8 @@ def test_fused_conv_epilogue(rng):
 
 
 def test_alignconv_f16_large_tile_variants(rng):
-    """the 128-position / wave-specialised kernels (picked when >= 512 tiles): f16, both layouts,
-    against the f16-column oracle on a random subset of positions (full oracle would take minutes)"""
+    """the patch-staged kernel (k_dcn_patch) on a launch of many full 8 x 16 tiles (512: two full rounds, the half-tile form is not
+    picked), fed from anchors: f16, both layouts, against the f16-column oracle on the first image"""
     import s2anet_amd as S
     from s2anet_amd.alignconv import align_conv_forward
     B, C, H, W, O, stride = 4, 128, 128, 128, 128, 8
@@ -1020,6 +1020,28 @@ def test_alignconv_f16_large_tile_variants(rng):
     offs = oracle.align_offsets(anchors[0].reshape(-1, 5), H, W, stride)[None]
     ref = oracle.deform_conv_forward(xh[:1].float().cpu().numpy(), offs, wh.float().cpu().numpy(), f16_cols=True, relu=True)
     err = np.abs(outs["nchw"][0] - ref[0])
+    assert err.max() < 3e-2 and err.mean() < 2e-3, (err.max(), err.mean())
+
+
+def test_dcn_f16_tall_map_fallback():
+    """a map side of 32000 does not fit the 16-bit coordinates of k_dcn_patch's sampling table: the launch falls back to
+    k_dcn_mfma on 64-position tiles (one channel chunk, one out-channel group, 4000 tiles of 128 positions).  f16, both
+    layouts, against the f16-column oracle on the WHOLE map (a cropped oracle differs: the large row coordinates round
+    differently in float); bounds of test_alignconv_f16_large_tile_variants (set for K = 1152 at these data scales; here
+    K = 576)"""
+    import s2anet_amd as S
+    B, C, O, H, W = 1, 64, 64, 32000, 16
+    g = np.random.default_rng(32000)
+    x = (g.standard_normal((B, C, H, W)) * 0.5).astype(np.float16).astype(np.float32)
+    w = (g.standard_normal((O, C, 3, 3)) * 0.05).astype(np.float16).astype(np.float32)
+    off = g.uniform(-2, 2, (B, 18, H, W)).astype(np.float32)
+    xh, wh = cu(x).half(), cu(w).half()
+    outs = {}
+    for name, xin in (("nchw", xh), ("nhwc", xh.contiguous(memory_format=torch.channels_last))):
+        outs[name] = S.deform_conv(xin, cu(off), wh, 1, 1, 1, 1, 1).float().cpu().numpy()
+    assert np.array_equal(outs["nchw"], outs["nhwc"])               # layout only changes storage
+    ref = oracle.deform_conv_forward(x, off, w, f16_cols=True)
+    err = np.abs(outs["nchw"] - ref)
     assert err.max() < 3e-2 and err.mean() < 2e-3, (err.max(), err.mean())
 
 

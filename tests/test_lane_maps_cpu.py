@@ -1,4 +1,4 @@
-"""The 16x16x32 lane maps of the convolution / AlignConv kernels (csrc/dcn_ops.hip: pix16, fbase16, abase16) restated on the host:
+"""The 16x16x32 lane maps of the convolution / AlignConv kernels (k_conv_f16 in csrc/conv_ops.hip, dcn_patch_tile in csrc/dcn_ops.hip: pix16, fbase16, abase16) restated on the host:
 every lane's pixel is distinct, the B-fragment and A-fragment ds_read_b128 are conflict-free on the 144-byte rows, and both operands
 address the same 8-channel group of the 64-channel chunk.  A device read of 16 B per lane is served in four groups of 16 lanes
 ({0-3,12-15,20-27}, {4-11,16-19,28-31} and the same + 32); a group is conflict-free when its sixteen 16-byte slots differ mod 16."""
