@@ -660,6 +660,16 @@ int s2a_conv3x3_head_pyramid_f16(const void* x, const void* weight_frag, const v
                                  const void* head_weight_frag, const void* head_bias, void* head_out,
                                  int64_t batch, int64_t channels, int64_t out_channels, int relu,
                                  const s2a_pyramid* pyr, s2a_stream_t stream);
+/* The 3x3 prediction convs with at most 16 maps (odm_reg_head: 5, odm_cls_head: num_classes <= 16; models/head.py:214-222):
+ * s2a_conv3x3_pyramid_f16 with out_channels = 64 on the same operands, but only the first 16 filter rows are multiplied
+ * (the filter stays in LDS, persistent workgroups walk the tiles).  weight_frag = s2a_conv_pack_weight_f16 of the [64,C,3,3]
+ * filter zero-padded from out_channels_used rows, bias = 64 f16 (zero beyond out_channels_used) or NULL, out[P,64]:
+ * columns < out_channels_used have the bits of s2a_conv3x3_pyramid_f16, the others are written as +0.  channels a multiple
+ * of 64, 1 <= out_channels_used <= 16.  S2A_CONV_NARROW=0 (and channels > 256: the filter no longer fits) sends the call to
+ * s2a_conv3x3_pyramid_f16; S2A_CONV_NARROW_WGS=n caps the persistent grid. */
+int s2a_conv3x3_narrow_pyramid_f16(const void* x, const void* weight_frag, const void* bias, void* out, int64_t batch,
+                                   int64_t channels, int64_t out_channels_used, int relu, const s2a_pyramid* pyr,
+                                   s2a_stream_t stream);
 /* ORConv2d + RotationInvariantPooling in one launch (models/head.py:337-341): out[P,O] = conv3x3(x) + bias (no
  * activation) and pooled[P,O/8] = max over every run of 8 orientation channels of out, both pyramid-packed. */
 int s2a_orconv_pool_pyramid_f16(const void* x, const void* weight_frag, const void* bias, void* out, void* pooled,

@@ -1028,6 +1028,213 @@ __global__ __launch_bounds__(256, 2) void k_conv1x1_chain_f16(const _Float16* __
   }
 }
 
+// ------------------------------------------------------------------ 3x3 prediction convs with <= 16 maps, persistent
+// odm_reg_head (256 -> 5) and odm_cls_head (256 -> 15), models/head.py:214-222, pyramid-packed.  Their filters are
+// zero-padded to 64 rows, and k_conv_f16<9, 1> multiplies all 64: three quarters of its MFMAs are zero rows, and each of
+// its four waves pulls the same 8 KB of filter fragments from L2 for every (chunk, tap).  Here only the first 16-row tile
+// of the 16x16x32 form runs (the a = 0 MFMAs of k_conv_f16, same B lane map, same K order chunk / tap / k-step, same
+// epilogue: every real output has the parent's bits), and the 16-row filter (2 KB per stage, 72 KB at 256 inputs) is
+// read out of the SAME packed buffer into LDS once per workgroup.  The workgroups are persistent: each walks a
+// contiguous run of 8 x 16 tiles (the halo columns two tiles of a run share are re-read by the same CU; runs of
+// workgroups with consecutive ids sit on different XCDs, so the halo rows between runs come through different L2s:
+// k_conv_f16's xcd_remap is not applied) and finds the level of every tile anew.  Three buffers hold 64-channel patch
+// chunks: while one is computed, the next one has been requested a stage earlier and the one after it -- chunks of the
+// next tile included -- is requested now, so two chunks are in flight (with two buffers and one chunk in flight the
+// waves waited at every stage's barrier: 43.9 us per launch against 40.2, docs/HISTORY.md "Round 8").
+// A wave owns two patch rows (2 x 16 positions): three ds_read_b128 per two MFMAs.
+constexpr int kNarrowPatch = ConvCfg<9, 1>::kPatchBytes;                  // 10 x 18 pixels x 144 B, in 1 KB DMA pieces
+constexpr int kNarrowJ = ConvCfg<9, 1>::kJ;
+constexpr int kNarrowDma = ConvCfg<9, 1>::kDma;
+constexpr int kNarrowOutBytes = 128 * 32;                                 // staged tile: 128 positions x 16 maps
+constexpr int kNarrowFixedLds = 3 * kNarrowPatch + 2 * kNarrowOutBytes + 64;  // three patch chunks: two in flight
+constexpr int kNarrowMaxC = 256;                                          // 18 KB of filter per 64 inputs: 161 856 B of 160 KiB
+inline int narrow_lds_bytes(int C) { return kNarrowFixedLds + (C / 64) * 9 * 2048; }
+
+__global__ __launch_bounds__(256, 1) void k_conv3x3_narrow_f16(const _Float16* __restrict__ x,
+                                                               const _Float16* __restrict__ wfrag,
+                                                               const _Float16* __restrict__ bias,
+                                                               _Float16* __restrict__ out, int C, int O_used, int relu,
+                                                               unsigned x_bytes, LevelTab lt, int tiles) {
+  using T = _Float16;
+  using V = f16x8;
+  using h2e = __attribute__((ext_vector_type(2))) _Float16;
+  using h4e = __attribute__((ext_vector_type(4))) _Float16;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+  const int CC = C / 64, nstage = 9 * CC;
+  char* s_w = smem + 3 * kNarrowPatch;                 // [stage][k-step][lane] x 16 B
+  char* s_out = s_w + nstage * 2048;                   // two staged tiles (by tile parity)
+  T* s_bias = reinterpret_cast<T*>(s_out + 2 * kNarrowOutBytes);
+  // this workgroup's run of tiles
+  const int t_begin = (int)((int64_t)blockIdx.x * tiles / gridDim.x);
+  const int t_end = (int)((int64_t)(blockIdx.x + 1) * tiles / gridDim.x);
+  if (t_begin >= t_end) return;
+  const unsigned row_bytes = (unsigned)C * 2;
+  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(x), 0, (int)x_bytes, 0x00020000);
+
+  struct Tile { int H, W, ty0, tx0; int64_t base; };   // base: packed pixel index of (image, 0, 0)
+  auto decode = [&](int tile) {
+    int t0 = 0, p0 = 0, H = lt.H[0], W = lt.W[0];
+#pragma unroll
+    for (int i = 1; i < kMaxLevels; i++)
+      if (i < lt.n && tile >= lt.tile0[i]) {
+        t0 = lt.tile0[i]; p0 = lt.pix0[i]; H = lt.H[i]; W = lt.W[i];
+      }
+    const int txn = (W + 15) / 16, tyn = (H + 7) / 8, loc = tile - t0;
+    const int bimg = loc / (txn * tyn), trem = loc % (txn * tyn);
+    return Tile{H, W, (trem / txn) * 8, (trem % txn) * 16, (int64_t)p0 + (int64_t)bimg * H * W};
+  };
+  // patch chunk -> LDS by LDS-DMA: slot layout and zero fill of k_conv_f16 (pixel * 9 + 16-byte piece, pad piece and
+  // pixels outside the image read out of range), one buffer descriptor over the whole packed input
+  unsigned pvoff[kNarrowJ];
+  auto bind = [&](const Tile& tl) {
+#pragma unroll
+    for (int j = 0; j < kNarrowJ; j++) {
+      const int v = (wave_u + 4 * j) * 64 + lane, p = v / 9, q = v % 9;
+      const int yy = tl.ty0 - 1 + p / kCPW, xx = tl.tx0 - 1 + p % kCPW;
+      const bool in = q < 8 && p < ConvCfg<9, 1>::kPix && yy >= 0 && yy < tl.H && xx >= 0 && xx < tl.W;
+      pvoff[j] = in ? (unsigned)((tl.base + (int64_t)yy * tl.W + xx) * row_bytes + q * 16) : 0x80000000u;
+    }
+  };
+  auto piece_issue = [&](int buf, int cc, int j) {      // piece j of this wave (7 cover the 26 of a chunk)
+    const int i = wave_u + 4 * j;
+    if (i < kNarrowDma)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)(smem + buf * kNarrowPatch + i * 1024),
+                                               16, (int)pvoff[j], cc * 128, 0, 0);
+  };
+  auto patch_issue = [&](int buf, int cc) {
+#pragma unroll
+    for (int j = 0; j < kNarrowJ; j++) piece_issue(buf, cc, j);
+  };
+
+  // issue cursor: the chunk that is requested next, two ahead of the one being computed
+  int itile = t_begin, icc = 0;
+  bool ivalid = true;
+  auto advance = [&]() {
+    if (++icc == CC) {
+      icc = 0;
+      if (++itile < t_end) bind(decode(itile)); else ivalid = false;
+    }
+  };
+  bind(decode(t_begin));
+  patch_issue(0, 0);
+  advance();
+  if (ivalid) {
+    patch_issue(1, icc);
+    advance();
+  }
+  // rows 0..15 of the packed filter: (stage s, k-step ks, lane l) is the fragment load_w reads for tile a = 0
+  for (int idx = tid; idx < nstage * 128; idx += 256) {
+    const int s = idx >> 7, ks = (idx >> 6) & 1, l = idx & 63;
+    *reinterpret_cast<V*>(s_w + idx * 16) =
+        reinterpret_cast<const V*>(wfrag)[(int64_t)s * 512 + ks * 64 + ((l >> 4) & 1) * 128 + (l >> 5) * 32 + (l & 15)];
+  }
+  if (tid < 16) s_bias[tid] = (bias && tid < O_used) ? bias[tid] : (T)0.f;
+
+  // lane maps of the 16x16x32 form (k_conv_f16): position pix16 of patch row 2 * wave + b, k-group kg16
+  const int kg16 = lane >> 4, i16 = lane & 15;
+  const int pix16 = (i16 >= 4 && i16 < 12) ? (((i16 - 4) >> 1) * 4 + (i16 & 1))
+                                           : (((i16 & 3) >> 1) * 4 + 2 + (i16 & 1) + (i16 >= 12 ? 8 : 0));
+  const int fbase16 = (2 * wave * kCPW + pix16) * kRowBytes + (kg16 & 1) * 64 + (kg16 >> 1) * 16;
+  constexpr int kTile16 = kCPW * kRowBytes;
+  const bool relu_u = __builtin_amdgcn_readfirstlane(relu) != 0;
+  f32x4 acc[2];
+#pragma unroll
+  for (int b = 0; b < 2; b++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) acc[b][r] = 0.f;
+  __syncthreads();      // first chunk, filter and bias in LDS
+
+  // end of a stage: this wave's pieces of the NEXT chunk have landed (vmcnt counts loads in order: only the pieces
+  // issued during this stage, `newest` of them, may still be in flight), its LDS writes are done, then the barrier.
+  // Written as one asm statement: in front of a barrier of its own the compiler waits for vmcnt(0), which would take
+  // the second chunk in flight away again.
+  auto stage_sync = [&](bool issued) {
+    __builtin_amdgcn_sched_barrier(0);
+    if (!issued) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    else if (wave_u + 4 * (kNarrowJ - 1) < kNarrowDma) asm volatile("s_waitcnt vmcnt(7) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  static_assert(kNarrowJ == 7 && kNarrowDma == 26, "stage_sync counts 7 pieces on waves 0-1 and 6 on waves 2-3");
+  int rb = 0;
+  for (int tile = t_begin; tile < t_end; tile++) {
+    const Tile cur = decode(tile);
+    bool issued = false;
+    for (int cc = 0; cc < CC; cc++) {
+      // the chunk two stages ahead (of this tile or of a later one) goes into the buffer every wave left at the last
+      // barrier: one DMA piece per tap, between the MFMAs
+      const bool more = ivalid;
+      issued = more;
+      const int ncc = icc, wb = rb == 0 ? 2 : rb - 1, buf = rb;
+      const char* P = smem + buf * kNarrowPatch + fbase16;
+      const char* Wc = s_w + cc * (9 * 2048) + lane * 16;
+      // fragments two taps ahead in registers (one wave per SIMD: nothing else covers the LDS latency)
+      V fa[3][2], fp[3][2][2];
+      auto load_tap = [&](int t, V (&a)[2], V (&p)[2][2]) {
+        const int toff = ((t / 3) * kCPW + (t % 3)) * kRowBytes;
+#pragma unroll
+        for (int ks = 0; ks < 2; ks++) {
+          a[ks] = *reinterpret_cast<const V*>(Wc + (t * 2 + ks) * 1024);
+          p[ks][0] = *reinterpret_cast<const V*>(P + toff + ks * 32);
+          p[ks][1] = *reinterpret_cast<const V*>(P + kTile16 + toff + ks * 32);
+        }
+      };
+      load_tap(0, fa[0], fp[0]);
+      load_tap(1, fa[1], fp[1]);
+#pragma unroll
+      for (int t = 0; t < 9; t++) {
+        if (t + 2 < 9) load_tap(t + 2, fa[(t + 2) % 3], fp[(t + 2) % 3]);
+        if (t < kNarrowJ && more) piece_issue(wb, ncc, t);
+#pragma unroll
+        for (int ks = 0; ks < 2; ks++) {
+          acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[t % 3][ks], fp[t % 3][ks][0], acc[0], 0, 0, 0);
+          acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[t % 3][ks], fp[t % 3][ks][1], acc[1], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (more) advance();                // (rebinds the patch offsets when the cursor enters a new tile)
+      rb = rb == 2 ? 0 : rb + 1;
+      if (cc + 1 < CC) stage_sync(more);  // the next chunk has landed; the buffer just read is free
+    }
+    // ---- epilogue of k_conv_f16: f32 sum + f16 bias, one f16 rounding, ReLU on the rounded halves; maps >= O_used are +0
+    char* so = s_out + ((tile - t_begin) & 1) * kNarrowOutBytes;
+    {
+      const int och = 4 * kg16;                      // D: row (out channel) = 4 (lane >> 4) + register, column = pixel
+      const h4e bq = *reinterpret_cast<const h4e*>(s_bias + och);
+#pragma unroll
+      for (int b = 0; b < 2; b++) {
+        h2e lo = {(_Float16)(acc[b][0] + (float)bq[0]), (_Float16)(acc[b][1] + (float)bq[1])};
+        h2e hi = {(_Float16)(acc[b][2] + (float)bq[2]), (_Float16)(acc[b][3] + (float)bq[3])};
+        if (relu_u) {
+          lo = __builtin_elementwise_max(lo, h2e{(_Float16)0.f, (_Float16)0.f});
+          hi = __builtin_elementwise_max(hi, h2e{(_Float16)0.f, (_Float16)0.f});
+        }
+        h4e v4 = {lo[0], lo[1], hi[0], hi[1]};
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+          if (och + e >= O_used) v4[e] = (_Float16)0.f;
+        *reinterpret_cast<h4e*>(so + (16 * (2 * wave + b) + pix16) * 32 + och * 2) = v4;
+#pragma unroll
+        for (int r = 0; r < 4; r++) acc[b][r] = 0.f;
+      }
+    }
+    stage_sync(issued);   // tile staged; the next tile's first chunk has landed and the buffer just read is free
+    // whole 128-byte rows: two vectors of maps, six of zeros (the 64-column buffer's padding, written as the parent does)
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const int idx = tid + 256 * i, pos = idx >> 3, col = idx & 7;
+      const int y = cur.ty0 + (pos >> 4), xq = cur.tx0 + (pos & 15);
+      V v;
+#pragma unroll
+      for (int e = 0; e < 8; e++) v[e] = (_Float16)0.f;
+      if (col < 2) v = *reinterpret_cast<const V*>(so + pos * 32 + col * 16);
+      if (y < cur.H && xq < cur.W) *reinterpret_cast<V*>(out + (cur.base + (int64_t)y * cur.W + xq) * 64 + col * 8) = v;
+    }
+  }
+}
+
 }  // namespace
 }  // namespace s2a
 
@@ -1335,4 +1542,38 @@ static int conv3x3_pyramid_impl(const void* x, const void* weight_frag, const vo
                    &lt, tiles, 0, ex};
   if (ph == 2 && og == 4) return c.run<9, 4, 2>();
   return og == 4 ? c.run<9, 4>() : (og == 2 ? c.run<9, 2>() : c.run<9, 1>());
+}
+
+extern "C" int s2a_conv3x3_narrow_pyramid_f16(const void* x, const void* weight_frag, const void* bias, void* out,
+                                              int64_t batch, int64_t channels, int64_t out_channels_used, int relu,
+                                              const s2a_pyramid* pyr, s2a_stream_t stream) {
+  S2A_CHECK_ARG(batch >= 0 && channels > 0, "conv_narrow_pyramid: bad shape");
+  S2A_CHECK_ARG(channels % 64 == 0, "conv_narrow_pyramid: channels must be a multiple of 64");
+  S2A_CHECK_ARG(out_channels_used >= 1 && out_channels_used <= 16, "conv_narrow_pyramid: 1..16 maps (out_channels_used)");
+  // S2A_CONV_NARROW=0: the 64-row launch (A/B switch); it also serves filters too large to stay in LDS
+  bool narrow = channels <= kNarrowMaxC;
+  if (const char* f = getenv("S2A_CONV_NARROW")) narrow = narrow && atoi(f) != 0;
+  if (!narrow)
+    return conv3x3_pyramid_impl(x, weight_frag, bias, nullptr, out, ConvExtra{nullptr, nullptr, nullptr, nullptr, 1}, batch,
+                                channels, 64, relu, pyr, stream);
+  LevelTab lt; int64_t pix = 0;
+  const int64_t tiles = build_levels(pyr, batch, &lt, &pix, 8);
+  S2A_CHECK_ARG(tiles >= 0, "conv_narrow_pyramid: bad level table (1..8 levels, positive sizes)");
+  S2A_CHECK_ARG((uint64_t)pix * channels * 2 < (1ull << 31), "conv_narrow_pyramid: input too large for 32-bit offsets");
+  if (batch == 0) return S2A_OK;
+  S2A_CHECK_ARG(x && weight_frag && out, "conv_narrow_pyramid: NULL tensor");
+  S2A_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)weight_frag % 16) == 0 &&
+                ((uintptr_t)bias % 8) == 0, "conv_narrow_pyramid: tensors must be 16-byte aligned");
+  // persistent grid: one workgroup fits a CU (LDS).  S2A_CONV_NARROW_WGS=n caps it (tests: one workgroup walks several levels)
+  int64_t grid = std::min<int64_t>(tiles, 256);
+  if (const char* f = getenv("S2A_CONV_NARROW_WGS")) grid = std::min<int64_t>(grid, std::max(1, atoi(f)));
+  const int lds = narrow_lds_bytes((int)channels);
+  auto kern = k_conv3x3_narrow_f16;
+  S2A_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  kern<<<dim3((unsigned)grid), 256, lds, as_stream(stream)>>>((const _Float16*)x, (const _Float16*)weight_frag,
+                                                               (const _Float16*)bias, (_Float16*)out, (int)channels,
+                                                               (int)out_channels_used, relu,
+                                                               (unsigned)((uint64_t)pix * channels * 2), lt, (int)tiles);
+  S2A_LAUNCH_CHECK();
+  return S2A_OK;
 }

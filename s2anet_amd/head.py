@@ -205,10 +205,11 @@ class S2ANetHead(nn.Module):
             or_feat = P.conv3x3(layout, al, orc.get(wa),
                                 orc.get_bias(self.or_conv.bias, wa.shape[0]), wa.shape[0], relu=False)
             pooled = P.rot_inv_pool(or_feat, self.or_pool.nOrientation)                     # [P,32]
-        w, b, o = self.odm_cls_head.packed_args()
-        odm_cls = P.conv3x3(layout, tower(self.odm_cls_ls, pooled), w, b, o, relu=False)    # [P,64], C used
-        w, b, o = self.odm_reg_head.packed_args()
-        odm_bbox = P.conv3x3(layout, tower(self.odm_reg_ls, or_feat), w, b, o, relu=False)  # [P,64], 5 used
+        # the real map counts: up to 16 maps run on 16 filter rows (pyramid.conv3x3); the buffers stay 64 columns wide
+        w, b, _ = self.odm_cls_head.packed_args()
+        odm_cls = P.conv3x3(layout, tower(self.odm_cls_ls, pooled), w, b, self.odm_cls_head.out_channels, relu=False)    # [P,64], C used
+        w, b, _ = self.odm_reg_head.packed_args()
+        odm_bbox = P.conv3x3(layout, tower(self.odm_reg_ls, or_feat), w, b, self.odm_reg_head.out_channels, relu=False)  # [P,64], 5 used
         n = len(layout.sizes)
         if trace is not None:
             trace.update(x=x, fam_bbox=fam_bbox, fam_cls=fam_cls, own_anchors=own_anchors, anchors=anchors, align=al,

@@ -50,8 +50,20 @@ class PyramidLayout:
 
 
 def conv3x3(layout, x, packed_w, bias, out_channels, relu, residual=None, out=None):
-    """3x3 / stride 1 / pad 1 on every level: x[P,C] -> out[P,O] (O multiple of 64)"""
+    """3x3 / stride 1 / pad 1 on every level: x[P,C] -> out[P,O] (O multiple of 64).
+    out_channels <= 16 (a prediction head: packed_w and bias zero-padded to 64 rows) without a residual: out[P,64] from
+    the 16-row kernel (s2a_conv3x3_narrow_pyramid_f16), the same bits in the first out_channels columns, +0 in the rest"""
     L = _lib.lib()
+    if out_channels <= 16 and residual is None and x.shape[1] % 64 == 0:
+        if out is None:
+            out = layout.new(64, x.device)
+        assert out.shape == (layout.pixels, 64) and out.is_contiguous(), "the 16-row kernel stores rows of 64 columns"
+        with torch.cuda.device(x.device):
+            _lib.check(L.s2a_conv3x3_narrow_pyramid_f16(_lib.ptr(x), _lib.ptr(packed_w), _lib.ptr(bias), _lib.ptr(out),
+                                                        layout.batch, x.shape[1], out_channels, int(bool(relu)),
+                                                        ctypes.byref(layout.c), _lib.stream_ptr(x.device)))
+        return out
+    out_channels = max(64, out_channels)
     if out is None:
         out = layout.new(out_channels, x.device)
     with torch.cuda.device(x.device):
