@@ -292,6 +292,13 @@ int s2a_rot_inv_pool_backward(const void* x, const void* grad_output, int64_t ba
  *                                    channel 2t = dy, 2t+1 = dx of tap t (kernel.cu:221-222)
  *   output [B,O,Ho,Wo]               dtype, `layout` storage, caller-allocated
  * relu != 0 fuses AlignConv's ReLU (models/alignconv.py:97).
+ *
+ * NaN and the fused ReLU, for EVERY `relu` argument of this header (deform / align convolutions, s2a_bias_act_nhwc,
+ * s2a_conv_nhwc_f16 and the pyramid, chain and tail launches built on it): the epilogue is max(v, 0) with the
+ * hardware's rule, which returns 0 for a NaN; +-inf keep their class (relu(-inf) = 0).  That is the inference
+ * contract.  A caller that needs torch's ReLU (NaN stays NaN), as training under a loss scale does, launches with
+ * relu = 0 and applies the ReLU itself; s2anet_amd's autograd functions do exactly that.  The backward entries
+ * (s2a_conv_backward_prep_f16) mask with out <= 0, so a gradient passes at a NaN output.
  * ------------------------------------------------------------------------- */
 typedef struct s2a_dcn_params {
   int64_t batch, channels, height, width, out_channels;
@@ -477,6 +484,7 @@ int s2a_bias_act_nhwc_to(const void* y, const void* bias, const void* residual, 
  * S2ANetHead (models/head.py:163-222, nn.Conv2d + nn.ReLU pairs) and the 1x1 layers of the carrier,
  * on the same patch-staged MFMA structure as AlignConv.  ksize 3: pad 1, stride 1 or 2 (stride 2: O % 128 == 0).
  * ksize 1: pad 0, stride 1 or 2.  x[B,H,W,C] -> out[B,Ho,Wo,O] = relu?(conv(x) + bias (+ residual[B,Ho,Wo,O])).
+ * The fused ReLU writes 0 for a NaN (see the note at s2a_dcn_params); relu = 0 hands every value on as it is.
  * weight_frag = s2a_conv_pack_weight_f16 of the [O,C,k,k] filter (O*C*k*k halfs, MFMA-fragment order);
  * bias[O] f16 or NULL; residual or NULL.  O must be a multiple of 64 (narrower heads: zero-pad the
  * filter), C a multiple of 64 or exactly 32 (then the filter given to s2a_conv_pack_weight_f16 is
@@ -495,7 +503,8 @@ int s2a_conv_nhwc_f16(const void* x, const void* weight_frag, const void* bias, 
  *   input-gradient filter w'[c,o,ky,kx] = w[o,c,k-1-ky,k-1-kx] (a [C,O,k,k] filter: s2a_conv_nhwc_f16 on the output gradient
  *   with it, channels = O, out_channels = C, gives the input gradient).
  * s2a_conv_backward_prep_f16: one pass over grad_out [positions, O] f16.  out (the forward's ReLU output, or NULL when no
- *   ReLU was fused): g = grad_out * (out > 0), written to g unless g is NULL.  grad_bias [O] (grad_bias_dtype, or NULL): the
+ *   ReLU was applied): g = out <= 0 ? 0 : grad_out (torch's rule: the gradient passes at a NaN output), written to g unless
+ *   g is NULL.  grad_bias [O] (grad_bias_dtype, or NULL): the
  *   per-channel sums of g (of grad_out without out), f32 partials per workgroup summed in workgroup order.  With neither g
  *   nor grad_bias nothing is launched.  workspace: only for grad_bias.
  * s2a_conv_backward_weight_f16: grad_weight[o,c,ky,kx] (grad_dtype, contiguous [O,C,k,k]) =

@@ -69,13 +69,14 @@ def align_conv_forward(x, anchors, weight, stride, relu=True, packed=False, out_
 
 class AlignConvFunction(torch.autograd.Function):
     """the fused AlignConv (align_conv_forward, ReLU included) with a backward: the sampling offsets are rebuilt with
-    align_offsets (the ones the unfused route feeds deform_conv), grad_output is masked by the saved output > 0 (the
-    fused ReLU), and the deformable-conv backward of DeformConvFunction gives the input and weight gradients.  The
+    align_offsets (the ones the unfused route feeds deform_conv), grad_output is masked by the saved output (zero where
+    out <= 0, so it passes at a NaN, as torch's ReLU), and the deformable-conv backward of DeformConvFunction gives the input and weight gradients.  The
     anchors get none (they are detached in the reference, models/head.py:322)."""
 
     @staticmethod
     def forward(ctx, x, anchors, weight, stride):
-        out = align_conv_forward(x, anchors, weight, stride, relu=True)
+        # the kernels' fused ReLU maps NaN to 0 (kept for inference); under autograd the stock in-place ReLU keeps it
+        out = align_conv_forward(x, anchors, weight, stride, relu=False).relu_()
         ctx.stride = stride
         ctx.save_for_backward(x, anchors, weight, out)
         return out

@@ -41,7 +41,8 @@ __global__ void k_conv_pack_train(const T* __restrict__ w, int O, int C, int tap
 }
 
 // ================================================================= backward preparation: ReLU mask + bias gradient
-// one pass over grad_out [P][O]: g = grad_out * (out > 0) (when out is given) and, when the bias gradient is wanted, the
+// one pass over grad_out [P][O]: g = out <= 0 ? 0 : grad_out (when out is given; selected, never multiplied: a NaN output
+// passes the gradient, as torch's ReLU does) and, when the bias gradient is wanted, the
 // per-channel f32 sums of g.  A workgroup owns a run of rows; thread (cx = tid & 7, ry = tid >> 3) takes the 8-channel
 // vectors cx, cx + 8, ... of rows ry, ry + 32, ...; the 32 row-partials of a vector are summed in ry order, the workgroups'
 // partials [workgroup][O] in workgroup order by k_conv_bwd_bias_final: no float atomics, the same bits every run.
@@ -72,7 +73,7 @@ __global__ __launch_bounds__(256) void k_conv_bwd_prep(const _Float16* __restric
         const f16x8b y = *reinterpret_cast<const f16x8b*>(out + at);
 #pragma unroll
         for (int j = 0; j < 8; j++)
-          if (!(y[j] > (_Float16)0.f)) v[j] = (_Float16)0.f;
+          if (y[j] <= (_Float16)0.f) v[j] = (_Float16)0.f;      // torch's rule: a NaN output passes the gradient
         if (g) *reinterpret_cast<f16x8b*>(g + at) = v;
       }
 #pragma unroll
@@ -230,9 +231,22 @@ __global__ __launch_bounds__(512, 2) void k_conv_bwd_weight(const _Float16* __re
     // group's 4 x 16 block and receives column (lane & 15) of the four rows; group gq covers rows 8 (gq >> 1) + 4 r .. + 3 of
     // the 16-position step ks and columns 16 (gq & 1) .. + 15.  Position 16 ks + p of a 3x3 tile is tile row ks, column p:
     // its tap-kx sample is patch pixel ks * 18 + p + kx (the patch rows are already shifted by ky).
+    // 3x3: tile positions outside the image hold g = 0, but their tap-shifted patch pixels can lie INSIDE it, and 0 * inf
+    // is NaN.  Such positions leave the contraction: a tile row below the image is skipped (ks >= rows_in), and in a tile
+    // that crosses the right edge the B elements of the columns past it are cleared (a lane's 8 elements of a fragment are
+    // columns 8 (gq >> 1) .. + 7 of tile row ks).  Both conditions are uniform; finite data sums the same bits as before.
+    int rows_in = 4, cols_in = 16;
+    if (KS == 3) {
+      const int r = tile % (tyn * txn);
+      rows_in = min(4, H - (r / txn) * 4);
+      cols_in = min(16, W - (r % txn) * 16);
+    }
     if (mwave) {
       const int gq = lane >> 4, qq = (lane >> 2) & 3, pp = lane & 3;
       const int prow = 8 * (gq >> 1) + qq;
+      s16x8b keep;
+#pragma unroll
+      for (int j = 0; j < 8; j++) keep[j] = 8 * (gq >> 1) + j < cols_in ? (short)-1 : (short)0;
       const char* a_base = s_go + prow * kGoPitch + (wave * 32 + 16 * (gq & 1) + 4 * pp) * 2;
       const char* b_base = s_patch + prow * kPatPitch + (16 * (gq & 1) + 4 * pp) * 2;
       auto tr = [&](const char* p) {
@@ -245,13 +259,15 @@ __global__ __launch_bounds__(512, 2) void k_conv_bwd_weight(const _Float16* __re
       };
 #pragma unroll
       for (int ks = 0; ks < kTPos / 16; ks++) {
+        if (KS == 3 && ks >= rows_in) continue;
         const f16x8b A = frag(a_base + ks * 16 * kGoPitch, kGoPitch);
 #pragma unroll
         for (int tl = 0; tl < KS; tl++)
 #pragma unroll
           for (int ct = 0; ct < 2; ct++) {
             const int pix0 = KS == 3 ? ks * kPatW + tl : ks * 16;
-            const f16x8b Bf = frag(b_base + pix0 * kPatPitch + ct * 64, kPatPitch);
+            f16x8b Bf = frag(b_base + pix0 * kPatPitch + ct * 64, kPatPitch);
+            if (KS == 3 && cols_in < 16) Bf = __builtin_bit_cast(f16x8b, __builtin_bit_cast(s16x8b, Bf) & keep);
             acc[tl][ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, Bf, acc[tl][ct], 0, 0, 0);
           }
       }

@@ -1282,10 +1282,12 @@ __global__ __launch_bounds__(512, 2) void k_dcn_bwd_weight(const _Float16* __res
         const f16x8b c0 = *reinterpret_cast<const f16x8b*>(p0), c1 = *reinterpret_cast<const f16x8b*>(p0 + 128);
         const f16x8b c2 = *reinterpret_cast<const f16x8b*>(p0 + kBPW * 128), c3 = *reinterpret_cast<const f16x8b*>(p0 + kBPW * 128 + 128);
         const float w0 = (float)tp.w[0], w1 = (float)tp.w[1], w2 = (float)tp.w[2], w3 = (float)tp.w[3];
+        // a corner with weight 0 (dropped, or the whole sample invalid) is not blended: 0 * inf is NaN
+        const f16x8b z = {}, d0 = w0 != 0.f ? c0 : z, d1 = w1 != 0.f ? c1 : z, d2 = w2 != 0.f ? c2 : z, d3 = w3 != 0.f ? c3 : z;
         f16x8b outv;
 #pragma unroll
         for (int j = 0; j < 8; j++)
-          outv[j] = (_Float16)(w0 * (float)c0[j] + w1 * (float)c1[j] + w2 * (float)c2[j] + w3 * (float)c3[j]);
+          outv[j] = (_Float16)(w0 * (float)d0[j] + w1 * (float)d1[j] + w2 * (float)d2[j] + w3 * (float)d3[j]);
         *reinterpret_cast<f16x8b*>(dst) = outv;
       } else {
         f16x8b outv = {};
@@ -1305,6 +1307,9 @@ __global__ __launch_bounds__(512, 2) void k_dcn_bwd_weight(const _Float16* __res
             }
           }
           const float w0 = (float)tp.w[0], w1 = (float)tp.w[1], w2 = (float)tp.w[2], w3 = (float)tp.w[3];
+#pragma unroll
+          for (int k = 0; k < 4; k++)            // (a clamped or dropped corner, weight 0, is not blended)
+            if ((float)tp.w[k] == 0.f) c4[k] = f16x8b{};
 #pragma unroll
           for (int j = 0; j < 8; j++)
             outv[j] = (_Float16)(w0 * (float)c4[0][j] + w1 * (float)c4[1][j] + w2 * (float)c4[2][j] + w3 * (float)c4[3][j]);

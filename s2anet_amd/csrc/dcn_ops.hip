@@ -340,7 +340,8 @@ __global__ __launch_bounds__(256, 1) void k_dcn_mfma(const T* __restrict__ x,   
 #pragma unroll
       for (int k = 0; k < 4; k++) {
         cw[it][k] = tp.w[k];
-        cv[it][k] = *reinterpret_cast<const V*>(x + (int64_t)tp.idx[k] * C + cc * KC + q * VEC);
+        // a dropped corner (outside the image: weight 0, index of the image's first pixel) is not loaded: 0 * inf is NaN
+        cv[it][k] = tp.w[k] != 0.f ? *reinterpret_cast<const V*>(x + (int64_t)tp.idx[k] * C + cc * KC + q * VEC) : V{};
       }
     }
     const T* wsrc = wp + ((int64_t)s * O + o0) * KC;
@@ -1093,7 +1094,8 @@ __global__ __launch_bounds__(512, 1) void k_dcn_x3(const float* __restrict__ x, 
 #pragma unroll
       for (int k = 0; k < 4; k++) {
         r_.cw[k] = tp.w[k];
-        r_.cv[k] = *reinterpret_cast<const f32x4*>(x + (int64_t)tp.idx[k] * C + cc * kX3KC + q * 4);
+        // (a dropped corner is not loaded: see k_dcn_mfma)
+        r_.cv[k] = tp.w[k] != 0.f ? *reinterpret_cast<const f32x4*>(x + (int64_t)tp.idx[k] * C + cc * kX3KC + q * 4) : f32x4{};
       }
     }
     const __bf16* wsrc = wp + (int64_t)s * 3 * O * kX3KC;

@@ -125,6 +125,9 @@ __global__ __launch_bounds__(kThreads) void k_loss_main(MainArgs a, const int64_
         } else {
           reg_sum += ad - 0.5f * beta;
           gk = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
+          // a non-finite delta gives a NaN gradient, as autograd of the reference's where(d < beta, ..) form does
+          // (0 * inf from the branch not taken): the overflow must reach the update's found_inf
+          if (!(ad <= 3.402823466e+38f)) gk = __builtin_nanf("");
         }
         mp.grad_bbox[i] = gk * fpn;
       }

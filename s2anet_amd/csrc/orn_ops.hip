@@ -262,7 +262,8 @@ extern "C" int s2a_rot_inv_pool(const void* x, int64_t batch, int64_t channels, 
 
 // ---------------------------------------------------------------- rotation-invariant pooling, backward
 // d/dx of max over each group of nOri consecutive channels: the group's gradient goes to its maximal orientation, the
-// LOWEST index on a tie (torch.max(dim) as rotation_invariant_pooling.py:19-27 uses it); every other channel gets 0.
+// LOWEST index on a tie and the FIRST NaN when there is one (torch.max(dim) as rotation_invariant_pooling.py:19-27 uses it,
+// and the value the forward returns); every other channel gets 0.
 // One thread per (n, group, pixel); every element of grad_input is written.
 namespace s2a {
 namespace {
@@ -284,9 +285,9 @@ __global__ void k_ripool_backward(const T* __restrict__ x, const T* __restrict__
     }
     float mx = (float)x[base];
     int d = 0;
-    for (int l = 1; l < n_ori; l++) {
+    for (int l = 1; l < n_ori && mx == mx; l++) {        // the forward's rule: the first NaN is the maximum
       const float v = (float)x[base + l * step];
-      if (v > mx) { mx = v; d = l; }
+      if (v > mx || v != v) { mx = v; d = l; }
     }
     const T gv = g[gi];
     for (int l = 0; l < n_ori; l++) gin[base + l * step] = l == d ? gv : (T)0.0f;

@@ -363,6 +363,8 @@ def train_kernels(module, enabled=True):
 class FusedConvFunction(torch.autograd.Function):
     """relu?(conv(x) + bias (+ residual)) with its backward on the own kernels.  x f16 channels-last; weight / bias f16
     or f32 (masters: rounded to f16 by the pack, gradients straight from the f32 sums); stride 1, 3x3 / pad 1 or 1x1.
+    Non-finite values follow torch: a NaN pre-activation stays NaN behind the ReLU, and the backward passes the gradient
+    unless out <= 0, so an overflow reaches the gradients and TrainUpdate's found_inf.
     The filter is packed on EVERY call (s2a_conv_pack_weight_train: forward order and input-gradient order in one
     launch), never cached: weights change every step, and a graph replay moves no version counter.  No host read,
     launch geometry from shapes only, workspaces from the torch allocator: forward + backward can be captured."""
@@ -379,7 +381,11 @@ class FusedConvFunction(torch.autograd.Function):
         with torch.cuda.device(x.device):
             _lib.check(L.s2a_conv_pack_weight_train(_lib.ptr(w), _lib.dtype_code(w), O, C, k, _lib.ptr(fwd), _lib.ptr(dgrad),
                                                     _lib.stream_ptr(x.device)))
-        out = conv_f16(x, fwd, None if bias is None else bias.detach(), O, k, 1, relu, residual)
+        # the launch's fused ReLU is inference's (NaN -> 0, include/s2anet_hip.h): training runs it with relu = 0 and
+        # applies the stock in-place ReLU, which keeps a NaN; the finite entries get the same bits either way
+        out = conv_f16(x, fwd, None if bias is None else bias.detach(), O, k, 1, False, residual)
+        if relu:
+            out.relu_()
         ctx.save_for_backward(x if need_w else None, out if relu else None, dgrad)
         ctx.geom = (tuple(x.shape), O, k, weight.dtype, None if bias is None else bias.dtype)
         return out
