@@ -697,6 +697,25 @@ int s2a_conv_wino_pack_weight_f16(const void* weight, int64_t out_channels, int6
 int s2a_conv3x3_wino_pyramid_f16(const void* x, const void* weight_wino, const void* bias, void* out, void* pooled,
                                  int64_t batch, int64_t channels, int64_t out_channels, int relu,
                                  const s2a_pyramid* pyr, s2a_stream_t stream);
+/* FP8 (OCP e4m3fn, one byte per value) form of the 256 -> 256 tower convolutions, on the block-scaled matrix instruction
+ * v_mfma_scale_f32_16x16x128_f8f6f4 with every block scale 1.0.  Opt-in (s2anet_amd.fp8); nothing else calls these.
+ *   s2a_quantize_e4m3        q[rows, channels] = e4m3_rne(clamp(f32(x[rows, channels] f16) * inv_scale, -448, 448)):
+ *                            round to nearest even, subnormals kept, +-inf -> +-448, NaN -> NaN; channels % 16 == 0
+ *   s2a_conv_pack_weight_fp8 the [O,C,3,3] filter given as e4m3 bytes -> the fragment order s2a_conv3x3_pyramid_fp8
+ *                            reads (O*C*9 bytes; a permutation only: quantise the filter first); O % 64 == 0, C % 128 == 0
+ *   s2a_conv3x3_pyramid_fp8  3x3 / stride 1 / pad 1 on every level of the pyramid-packed x_q[P,C] e4m3:
+ *                            acc[o] = sum x_q * w_q in f32, v = fma(acc, scale[o], bias[o]) (scale = input scale * filter
+ *                            scale of channel o, f32[O]; bias f32[O]), optional ReLU (NaN -> 0), then
+ *                            out_e4m3 = 0: out[P,O] f16 = f16_rne(v)
+ *                            out_e4m3 = 1: out[P,O] e4m3 = e4m3_rne(clamp(v * out_inv_scale, -448, 448)): the next fp8
+ *                            layer's input without a quantise launch
+ *                            C % 128 == 0, O % 64 == 0; anything else is refused before any launch. */
+int s2a_quantize_e4m3(const void* x, void* q, int64_t rows, int64_t channels, float inv_scale, s2a_stream_t stream);
+int s2a_conv_pack_weight_fp8(const void* weight_q, int64_t out_channels, int64_t channels, void* packed,
+                             s2a_stream_t stream);
+int s2a_conv3x3_pyramid_fp8(const void* x_q, const void* weight_frag, const float* scale, const float* bias, void* out,
+                            int out_e4m3, float out_inv_scale, int64_t batch, int64_t channels, int64_t out_channels,
+                            int relu, const s2a_pyramid* pyr, s2a_stream_t stream);
 int s2a_align_conv_pyramid_f16(const void* x, const float* anchors, const void* weight_packed, void* out,
                                int64_t batch, int64_t channels, int64_t out_channels, int relu,
                                const s2a_pyramid* pyr, s2a_stream_t stream);

@@ -16,6 +16,7 @@ from .fused import drop_weight_caches, train_kernels, train_conv_ok, FusedConv2d
 from .scene import tile_grid, chip_names, gather_chips, merge_detections, SceneDetections
 from .evaluate import evaluate_task1, Task1Evaluator, Task1Result, claim_tp_fp
 from .optim import TrainUpdate, reference_param_groups, reference_lr
+from .fp8 import quantize_weight_e4m3, calibrate_fp8, fp8_towers
 
 __all__ = [
     "box_iou_rotated", "nms_rotated", "ml_nms_rotated", "multiclass_nms_rotated",
@@ -27,4 +28,5 @@ __all__ = [
     "evaluate_task1", "Task1Evaluator", "Task1Result", "claim_tp_fp",
     "TrainUpdate", "reference_param_groups", "reference_lr",
     "train_kernels", "train_conv_ok", "FusedConv2d", "FusedConvFunction",
+    "quantize_weight_e4m3", "calibrate_fp8", "fp8_towers",
 ]

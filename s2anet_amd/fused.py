@@ -96,6 +96,19 @@ def conv_pack_weight(weight):
     return out
 
 
+def conv_pack_weight_fp8(weight, in_scale):
+    """[O,C,3,3] -> (the e4m3 filter in the fragment order of s2a_conv3x3_pyramid_fp8, uint8 [O*C*9];
+    scale f32[O] = in_scale * s_w[o]): per-output-channel quantisation (fp8.quantize_weight_e4m3) + a byte permutation"""
+    from .fp8 import quantize_weight_e4m3
+    wq, s_w = quantize_weight_e4m3(weight)
+    O, C = wq.shape[:2]
+    assert tuple(wq.shape[2:]) == (3, 3) and O % 64 == 0 and C % 128 == 0
+    out = torch.empty((wq.numel(),), dtype=torch.uint8, device=wq.device)
+    with torch.cuda.device(wq.device):
+        _lib.check(_lib.lib().s2a_conv_pack_weight_fp8(_lib.ptr(wq), O, C, _lib.ptr(out), _lib.stream_ptr(wq.device)))
+    return out, (s_w * float(in_scale)).contiguous()
+
+
 def conv_wino_pack_weight(weight):
     """[O,C,3,3] -> the transformed filter of the Winograd F(2,3) kernel in fragment order (s2a_conv_wino_pack_weight_f16);
     O a multiple of 64, C a multiple of 32"""
@@ -292,6 +305,14 @@ class PackedWeightCache:
     def get(self, w):
         return self.lookup("direct", w, None, conv_pack_weight, w)
 
+    def get_fp8(self, w, in_scale):
+        """(e4m3 fragment-order filter, scale f32[O] = in_scale * s_w) of a [O,C,3,3] weight; the input scale is part of the
+        key, so a re-calibration makes a new entry"""
+        return self.lookup("fp8", w, float(in_scale), conv_pack_weight_fp8, w, float(in_scale))
+
+    def get_bias_f32(self, b):
+        return self.lookup("bias_f32", b, None, lambda t: t.detach().float().contiguous(), b)
+
     def get_bias(self, b, width):
         """f16 bias zero-padded to the physical channel count"""
         if b is None:
@@ -446,6 +467,20 @@ class FusedConv2d(nn.Conv2d):
             self._packed = PackedWeightCache()
         width = max(64, self.out_channels)
         return self._packed.get(self.weight), self._packed.get_bias(self.bias, width), width
+
+    def fp8_ok(self):
+        """a layer the e4m3 kernel serves: 3x3 / stride 1 / pad 1 with bias, O a multiple of 64, C a multiple of 128"""
+        return (tuple(self.kernel_size) == (3, 3) and tuple(self.stride) == (1, 1) and tuple(self.padding) == (1, 1) and
+                tuple(self.dilation) == (1, 1) and self.groups == 1 and self.bias is not None and
+                self.out_channels % 64 == 0 and self.in_channels % 128 == 0)
+
+    def packed_args_fp8(self, in_scale):
+        """(e4m3 filter, scale f32[O], bias f32[O], out channels) for s2a_conv3x3_pyramid_fp8 on an input quantised with
+        in_scale (x = in_scale * x_q)"""
+        if not hasattr(self, "_packed"):
+            self._packed = PackedWeightCache()
+        w, sc = self._packed.get_fp8(self.weight, in_scale)
+        return w, sc, self._packed.get_bias_f32(self.bias), self.out_channels
 
     def wino_ok(self):
         """a layer the Winograd kernel serves: 3x3 / stride 1 / pad 1, O a multiple of 64, C a multiple of 32"""

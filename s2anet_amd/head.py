@@ -73,6 +73,10 @@ class PyramidPred(tuple):
 
 
 class S2ANetHead(nn.Module):
+    # opt-in e4m3 tower route (s2anet_amd/fp8.py: calibrate_fp8 / fp8_towers); plain attributes, not buffers
+    fp8_enabled = False
+    fp8_scales = None
+
     def __init__(self, num_classes, in_channels=256, feat_channels=256, stacked_convs=2,
                  with_orconv=True, anchor_scales=(4,), featmap_strides=(8, 16, 32, 64, 128),
                  score_thres_before_nms=0.05, iou_thres_nms=0.5, max_before_nms_per_level=2000,
@@ -158,14 +162,33 @@ class S2ANetHead(nn.Module):
 
         wino = P.wino_enabled()
 
-        def tower(seq, t):
-            for blk in seq:
+        # opt-in e4m3 route of the plain 256 -> 256 tower launches (s2anet_amd/fp8.py): per-tensor activation scales fixed at
+        # calibration (host floats: nothing is read back)
+        fp8 = self.fp8_scales if self.fp8_enabled else None
+
+        def tower(seq, t, name=None):
+            for i, blk in enumerate(seq):
                 if wino and blk[0].wino_ok() and blk[0].in_channels >= 128:     # Winograd F(2,3) along x (wino_ops.hip)
                     w, b, o = blk[0].packed_args_wino()
                     t = P.conv3x3_wino(layout, t, w, b, o, relu=True)
-                    continue
-                w, b, o = blk[0].packed_args()
-                t = P.conv3x3(layout, t, w, b, o, relu=True)
+                else:
+                    w, b, o = blk[0].packed_args()
+                    t = P.conv3x3(layout, t, w, b, o, relu=True)
+                if trace is not None and name is not None:
+                    trace[f"{name}{i}"] = t
+            return t
+
+        def quantize(t, name):
+            return P.quantize_e4m3(t, 1.0 / fp8[name])
+
+        def tower_fp8(blk, tq, name, in_name, out_name=None):
+            """one tower layer on the e4m3 kernel: tq quantised with fp8[in_name]; out_name: write e4m3 with that scale
+            (the next fp8 layer's input) instead of f16"""
+            w, sc, b, o = blk[0].packed_args_fp8(fp8[in_name])
+            t = P.conv3x3_fp8(layout, tq, w, sc, b, o, relu=True, out_e4m3=out_name is not None,
+                              out_inv_scale=1.0 if out_name is None else 1.0 / fp8[out_name])
+            if trace is not None:
+                trace.update({f"fp8.{name}.in": tq, f"fp8.{name}.scale": sc, f"fp8.{name}.out": t})
             return t
 
         def tower_with_head(seq, head, t):
@@ -180,10 +203,17 @@ class S2ANetHead(nn.Module):
             hw, hb, _ = head.packed_args()
             return P.conv3x3_head(layout, t, w, b, o, hw, hb, relu=True)
 
-        fam_bbox = tower_with_head(self.fam_reg_ls, self.fam_reg_head, x)                   # [P,64], 5 used
         fam_cls = None
-        if self.compute_fam_cls:
-            fam_cls = tower_with_head(self.fam_cls_ls, self.fam_cls_head, x)
+        if fp8 is not None:      # x quantised once for both FAM towers; their second layers stay the fused f16 3x3 + 1x1 launch
+            xq = quantize(x, "x")
+            fam_bbox = tower_with_head(self.fam_reg_ls[1:], self.fam_reg_head, tower_fp8(self.fam_reg_ls[0], xq, "fam_reg_ls.0", "x"))
+            if self.compute_fam_cls:
+                fam_cls = tower_with_head(self.fam_cls_ls[1:], self.fam_cls_head,
+                                          tower_fp8(self.fam_cls_ls[0], xq, "fam_cls_ls.0", "x"))
+        else:
+            fam_bbox = tower_with_head(self.fam_reg_ls, self.fam_reg_head, x)               # [P,64], 5 used
+            if self.compute_fam_cls:
+                fam_cls = tower_with_head(self.fam_cls_ls, self.fam_cls_head, x)
         own_anchors = P.fam_refine_anchors(layout, fam_bbox, self.anchor_scale)             # [P,5] f32
         if anchors is None:
             anchors = own_anchors
@@ -206,10 +236,21 @@ class S2ANetHead(nn.Module):
                                 orc.get_bias(self.or_conv.bias, wa.shape[0]), wa.shape[0], relu=False)
             pooled = P.rot_inv_pool(or_feat, self.or_pool.nOrientation)                     # [P,32]
         # the real map counts: up to 16 maps run on 16 filter rows (pyramid.conv3x3); the buffers stay 64 columns wide
+        if fp8 is not None:
+            # the 32 -> 256 layer stays f16 and its output is quantised; odm_reg_ls[0] hands e4m3 straight to odm_reg_ls[1]
+            cls_t = tower_fp8(self.odm_cls_ls[1], quantize(tower(self.odm_cls_ls[:1], pooled, "odm_cls_ls"), "odm_cls_ls0"),
+                              "odm_cls_ls.1", "odm_cls_ls0")
+            reg_q = tower_fp8(self.odm_reg_ls[0], quantize(or_feat, "or_feat"), "odm_reg_ls.0", "or_feat", "odm_reg_ls0")
+            reg_t = tower_fp8(self.odm_reg_ls[1], reg_q, "odm_reg_ls.1", "odm_reg_ls0")
+        else:
+            cls_t = tower(self.odm_cls_ls, pooled, "odm_cls_ls")
+            reg_t = None      # (the f16 route keeps its launch order: the regression tower follows the classification head)
         w, b, _ = self.odm_cls_head.packed_args()
-        odm_cls = P.conv3x3(layout, tower(self.odm_cls_ls, pooled), w, b, self.odm_cls_head.out_channels, relu=False)    # [P,64], C used
+        odm_cls = P.conv3x3(layout, cls_t, w, b, self.odm_cls_head.out_channels, relu=False)    # [P,64], C used
+        if reg_t is None:
+            reg_t = tower(self.odm_reg_ls, or_feat, "odm_reg_ls")
         w, b, _ = self.odm_reg_head.packed_args()
-        odm_bbox = P.conv3x3(layout, tower(self.odm_reg_ls, or_feat), w, b, self.odm_reg_head.out_channels, relu=False)  # [P,64], 5 used
+        odm_bbox = P.conv3x3(layout, reg_t, w, b, self.odm_reg_head.out_channels, relu=False)  # [P,64], 5 used
         n = len(layout.sizes)
         if trace is not None:
             trace.update(x=x, fam_bbox=fam_bbox, fam_cls=fam_cls, own_anchors=own_anchors, anchors=anchors, align=al,

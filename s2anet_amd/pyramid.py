@@ -99,6 +99,39 @@ def orconv_pool(layout, x, packed_w, bias, out_channels, n_orientation=8):
     return out, pooled
 
 
+def quantize_e4m3(x, inv_scale, out=None):
+    """x[P,C] f16 -> uint8 [P,C] holding OCP e4m3fn bytes: e4m3_rne(clamp(f32(x) * inv_scale, -448, 448)), round to nearest
+    even, subnormals kept, +-inf -> +-448, NaN -> NaN (s2a_quantize_e4m3); C a multiple of 16"""
+    _lib.require_cuda(x)
+    assert x.dtype == torch.float16 and x.dim() == 2 and x.is_contiguous()
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    assert out.shape == x.shape and out.dtype == torch.uint8 and out.is_contiguous()
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().s2a_quantize_e4m3(_lib.ptr(x), _lib.ptr(out), x.shape[0], x.shape[1], float(inv_scale),
+                                                _lib.stream_ptr(x.device)))
+    return out
+
+
+def conv3x3_fp8(layout, xq, packed, scale, bias, out_channels, relu, out_e4m3=False, out_inv_scale=1.0, out=None):
+    """3x3 / stride 1 / pad 1 on every level with e4m3 operands (s2a_conv3x3_pyramid_fp8): xq[P,C] uint8 (e4m3 bytes),
+    packed = fused.conv_pack_weight_fp8's filter, scale / bias f32[O]: v = (sum x_q w_q) * scale[o] + bias[o], ReLU?;
+    -> out[P,O] f16, or with out_e4m3 uint8 [P,O] = e4m3_rne(clamp(v * out_inv_scale, -448, 448)).
+    C a multiple of 128, O a multiple of 64"""
+    assert xq.dtype == torch.uint8 and xq.shape[0] == layout.pixels and xq.is_contiguous()
+    assert scale.dtype == torch.float32 and bias.dtype == torch.float32 and scale.numel() == out_channels == bias.numel()
+    dt = torch.uint8 if out_e4m3 else torch.float16
+    if out is None:
+        out = layout.new(out_channels, xq.device, dt)
+    assert out.shape == (layout.pixels, out_channels) and out.dtype == dt and out.is_contiguous()
+    with torch.cuda.device(xq.device):
+        _lib.check(_lib.lib().s2a_conv3x3_pyramid_fp8(_lib.ptr(xq), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(bias), _lib.ptr(out),
+                                                      int(bool(out_e4m3)), float(out_inv_scale), layout.batch, xq.shape[1],
+                                                      out_channels, int(bool(relu)), ctypes.byref(layout.c),
+                                                      _lib.stream_ptr(xq.device)))
+    return out
+
+
 def conv3x3_wino(layout, x, packed_wino, bias, out_channels, relu, pool=False, out=None):
     """3x3 / stride 1 / pad 1 on every level in the Winograd F(2,3)-along-x form (s2a_conv3x3_wino_pyramid_f16):
     x[P,C] -> out[P,O]; pool: also the orientation max-pool [P,O/8] of the result (ORConv2d + RotationInvariantPooling)"""
