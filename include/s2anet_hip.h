@@ -16,7 +16,11 @@
  * the Python host side maps S2A_E* back to RuntimeError.
  *
  * Workspaces: ops that need scratch take (workspace, workspace_bytes); query the
- * size with the matching *_workspace_bytes().  Nothing in this library calls
+ * size with the matching *_workspace_bytes() (0: the sizes are ones the op refuses).
+ * Exactly that many bytes suffice; their contents on entry are arbitrary (nothing
+ * needs zeroing) and no result depends on them; nothing outside them is written;
+ * fewer bytes, or a NULL workspace, return S2A_EWORKSPACE before the first launch
+ * (tests/test_gpu_workspace_contract.py).  Nothing in this library calls
  * hipMalloc/hipFree/hipDeviceSynchronize on the hot path, so every launch
  * sequence is hipGraph-capturable; the only host synchronisations are the
  * explicitly documented `host_count` read-backs of the reference-shaped NMS calls.
@@ -152,8 +156,9 @@ int s2a_nms_poly(const double* dets9, int64_t n, double thresh, int64_t* keep, i
  * Everything — sort, pair finding, exact IoU, greedy resolution, compaction — runs on the
  * device; the reference's N x N/64 mask and its device->host copy (cuda.cu:109) do not exist here:
  * suppressing pairs are kept as a list.  s2a_nms_rotated_workspace_bytes() sizes the lists for
- * dense inputs; a SMALLER workspace (>= the fixed part + 48 KB) is accepted, and a call whose
- * lists fill up finishes on a slower memory-free kernel with the same keep list.
+ * dense inputs.  The two ops declared here take (n, n).  The segmented forms below accept a SMALLER one, down to
+ * s2a_nms_rotated_workspace_bytes(n, 1) (they are not told the max_segment_rows a caller sized for, so that is the
+ * bound they check): a call whose lists fill up finishes on a slower memory-free kernel with the same keep list.
  * Speed limit of the label handling (results are unaffected): inputs of more than 4 096 rows per label are ordered
  * spatially by an own counting sort whose tables hold at most 8 192 DISTINCT labels and 65 536 (label, cell) buckets;
  * beyond either the same memory-free kernel settles the call -- exact, but an order of magnitude slower (12 000 distinct
@@ -833,7 +838,9 @@ int s2a_s2anet_loss_backward(const s2a_loss_grad_map* maps, int n_maps, const fl
  * stats f32 [S2A_OPTIM_STATS] = (unscaled pre-clip gradient norm (0 when launch 1 is skipped), clip, found_inf,
  * skip_update, new scale, d, updates, growth_tracker).
  * Rows whose four pointers are all 16-byte aligned are walked with 16-byte accesses, others and tails element-wise.
- * workspace: s2a_train_update_workspace_bytes(n_trained_chunks), 16-byte aligned. */
+ * workspace: s2a_train_update_workspace_bytes(n_trained_chunks), 16-byte aligned.  It need NOT be zeroed, on the first
+ * call or any later one: launch 1 writes the partial and flag of every trained chunk and launch 2 every field of the control
+ * block before anything reads them (the Python side's zeroed buffer is a habit, not a requirement). */
 #define S2A_OPTIM_CHUNK 4096
 #define S2A_OPTIM_STATS 8
 #define S2A_OPTIM_TRAINED 0

@@ -388,6 +388,7 @@ extern "C" int s2a_assign_labels_batched(const s2a_anchor_set* sets, int num_set
   const AbSets t = {set_ptr[0], set_ptr[1], set_ptr[2], set_ptr[3], set_stride[0], set_stride[1], set_stride[2], set_stride[3]};
   S2A_CHECK_ARG(min_pos_iou_thr >= 0.f && pos_iou_thr > 0.f,
                 "assign_labels_batched: needs min_pos_iou_thr >= 0 and pos_iou_thr > 0 (unlisted pairs count as exact zeros)");
+  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, s2a_assign_labels_batched_workspace_bytes(S, B, A, G, P), "assign_labels_batched");
   S2A_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "assign_labels_batched: workspace must be 16-byte aligned");
   Carver cv(workspace, workspace_bytes);
   AbWs w;

@@ -62,6 +62,17 @@ int launch_keep_compact(const uint8_t* keep_orig, const int32_t* order, int64_t 
     }                                     \
   } while (0)
 
+// The workspace contract of include/s2anet_hip.h ("Workspaces"): fewer bytes than the op's *_workspace_bytes() query, or no
+// buffer at all, is S2A_EWORKSPACE -- in front of the first launch, after the argument checks (a refused size has no query).
+#define S2A_CHECK_WORKSPACE(ws, bytes, need, who)                                                      \
+  do {                                                                                                 \
+    const size_t need_ = (need);                                                                       \
+    if ((ws) == nullptr || (size_t)(bytes) < need_) {                                                  \
+      s2a::set_error("%s: workspace too small (%zu < %zu bytes)", who, (ws) ? (size_t)(bytes) : (size_t)0, need_); \
+      return S2A_EWORKSPACE;                                                                           \
+    }                                                                                                  \
+  } while (0)
+
 #define S2A_HIP(expr)                                                              \
   do {                                                                             \
     hipError_t e_ = (expr);                                                        \

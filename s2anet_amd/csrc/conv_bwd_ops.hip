@@ -2,6 +2,8 @@
 // preparation pass (ReLU mask + bias gradient) and the weight gradient.  The input gradient needs no kernel of its own: for a
 // stride-1 3x3 / pad-1 or 1x1 convolution it is s2a_conv_nhwc_f16 on the transposed, 180-degree-rotated filter, which the pack
 // below writes next to the forward filter.
+#include <algorithm>
+
 #include "common.hpp"
 
 namespace s2a {
@@ -363,11 +365,8 @@ extern "C" int s2a_conv_backward_prep_f16(const void* grad_out, const void* out,
   const int nb = prep_blocks(positions);
   float* partial = nullptr;
   if (grad_bias) {
-    const size_t need = s2a_conv_backward_prep_f16_workspace_bytes(positions, out_channels);
-    if (!workspace || workspace_bytes < need) {
-      set_error("conv_backward_prep: workspace too small (%zu < %zu bytes)", workspace ? workspace_bytes : (size_t)0, need);
-      return S2A_EWORKSPACE;
-    }
+    S2A_CHECK_WORKSPACE(workspace, workspace_bytes, s2a_conv_backward_prep_f16_workspace_bytes(positions, out_channels),
+                        "conv_backward_prep_f16");
     partial = (float*)workspace;
   }
   hipStream_t st = as_stream(stream);
@@ -397,7 +396,11 @@ extern "C" size_t s2a_conv_backward_weight_f16_workspace_bytes(int64_t batch, in
                                                                int64_t out_channels, int ksize) {
   if (!wgrad_shape_ok(batch, channels, height, width, out_channels, ksize) || batch == 0) return 0;
   const WgradGeom q = wgrad_geom(batch, channels, height, width, out_channels, ksize);
-  return align_up((size_t)q.ksplit * q.nowner * q.ostride * ksize * 64 * sizeof(float));
+  // (the launch writes ksplit * nowner blocks, at most the count it aims at while nowner is below it; the query declares that
+  // count itself, so that it never shrinks when a size grows: 255 blocks at 64 channels, 252 at 128)
+  const size_t aim = ksize == 3 ? kWgradBlocks3 : kWgradBlocks1;
+  const size_t blocks = std::max((size_t)q.ksplit * q.nowner, std::max(aim, (size_t)q.nowner));
+  return align_up(blocks * q.ostride * ksize * 64 * sizeof(float));
 }
 
 extern "C" int s2a_conv_backward_weight_f16(const void* x, const void* g, void* grad_weight, int grad_dtype, int64_t batch,
@@ -413,11 +416,9 @@ extern "C" int s2a_conv_backward_weight_f16(const void* x, const void* g, void* 
   S2A_CHECK_ARG(x && g && grad_weight, "conv_backward_weight: NULL tensor");
   S2A_CHECK_ARG(aligned16(x) && aligned16(g) && aligned16(grad_weight) && aligned16(workspace),
                 "conv_backward_weight: tensors must be 16-byte aligned");
-  const size_t need = s2a_conv_backward_weight_f16_workspace_bytes(batch, channels, height, width, out_channels, ksize);
-  if (!workspace || workspace_bytes < need) {
-    set_error("conv_backward_weight: workspace too small (%zu < %zu bytes)", workspace ? workspace_bytes : (size_t)0, need);
-    return S2A_EWORKSPACE;
-  }
+  S2A_CHECK_WORKSPACE(workspace, workspace_bytes,
+                      s2a_conv_backward_weight_f16_workspace_bytes(batch, channels, height, width, out_channels, ksize),
+                      "conv_backward_weight_f16");
   const WgradGeom q = wgrad_geom(batch, channels, height, width, out_channels, ksize);
   S2A_CHECK_ARG(q.ntiles < (1ll << 31) && (int64_t)q.ksplit * q.nowner < (1ll << 31), "conv_backward_weight: too many tiles");
   hipStream_t st = as_stream(stream);

@@ -2214,6 +2214,8 @@ struct FusedBwdArgs {
 };
 
 size_t fused_bwd_workspace(int dtype, bool want_input, bool want_weight, int64_t B, int64_t C, int64_t H, int64_t W, int64_t O) {
+  // (sizes and types the entry points refuse have no workspace: 0, as the other queries answer them)
+  if ((dtype != S2A_DTYPE_F16 && dtype != S2A_DTYPE_F32) || B < 0 || C <= 0 || H < 3 || W < 3 || O <= 0) return 0;
   const size_t el = dtype == S2A_DTYPE_F16 ? 2 : 4;
   size_t n = align_up((size_t)(B * H * W * C) * el) + align_up((size_t)(B * H * W * O) * el) + 1024;
   if (want_input) n += align_up((size_t)(O * C * 9) * el) + (dtype == S2A_DTYPE_F16 ? align_up((size_t)(B * H * W * C) * 4) : 0);
@@ -2237,10 +2239,10 @@ int fused_bwd_run(const FusedBwdArgs& a, void* workspace, size_t workspace_bytes
   S2A_CHECK_ARG(a.input && a.offset && a.grad_output, "%s: NULL tensor", who);
   S2A_CHECK_ARG(!want_input || (a.weight && a.grad_offset), "%s: NULL tensor", who);
   // (the workspace is carved into 16-byte vector buffers; a typed f32 gradInput is cleared with 16-byte stores, k_bwd_zero4)
+  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, fused_bwd_workspace(a.dtype, want_input, want_weight, B, C, H, W, O), who);
   S2A_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
   S2A_CHECK_ARG(kHalf || !want_input || !a.grad_input_typed || (reinterpret_cast<uintptr_t>(a.grad_input) & 15) == 0,
                 "%s: a float32 grad_input must be 16-byte aligned", who);
-  S2A_CHECK_ARG(workspace_bytes >= fused_bwd_workspace(a.dtype, want_input, want_weight, B, C, H, W, O), "%s: workspace too small", who);
   Carver cv(workspace, workspace_bytes);
   const int64_t HW = H * W;
   T* xn = cv.take<T>((size_t)(B * HW * C));
@@ -2249,7 +2251,10 @@ int fused_bwd_run(const FusedBwdArgs& a, void* workspace, size_t workspace_bytes
   // f16: [S,H,W,C] f32 accumulator the tiles' atomics add into (128-byte rows); f32: the caller's gradInput itself
   float* gacc = (want_input && kHalf) ? cv.take<float>((size_t)(B * HW * C)) : nullptr;
   float* partial = want_weight ? cv.take<float>((size_t)kWgradMaxBlocks * O * 192) : nullptr;
-  S2A_CHECK_ARG(xn && gn && (!want_input || (wp && (gacc || !kHalf))) && (!want_weight || partial), "%s: workspace too small", who);
+  if (!(xn && gn && (!want_input || (wp && (gacc || !kHalf))) && (!want_weight || partial))) {
+    set_error("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, cv.off);
+    return S2A_EWORKSPACE;
+  }
   // (an own fill kernel, not hipMemsetAsync: memset nodes of a captured graph are not replayed correctly on ROCm 7.2, DESIGN 5 --
   // a backward captured into a HIP graph would otherwise sum into a stale accumulator from its second replay on)
   if (want_input && (kHalf || a.grad_input_typed)) {

@@ -1448,7 +1448,9 @@ int run_fast(const void* input, const float* src, bool from_anchors, const void*
 using namespace s2a;
 
 extern "C" size_t s2a_deform_conv_workspace_bytes(const s2a_dcn_params* p) {
-  if (!p) return 0;
+  if (!p || p->batch < 0 || p->channels <= 0 || p->out_channels <= 0 || p->height <= 0 || p->width <= 0 || p->kH <= 0 || p->kW <= 0 ||
+      (p->dtype != S2A_DTYPE_F32 && p->dtype != S2A_DTYPE_F16 && p->dtype != S2A_DTYPE_F64))
+    return 0;   // (parameters the entry point refuses)
   size_t es = esize(p->dtype);
   size_t b = align_up((size_t)p->out_channels * p->channels * p->kH * p->kW * es * 3) + 256;      // packed filter: f16 two layouts, f32 2.5 x
   if (p->layout == S2A_LAYOUT_NCHW) b += align_up((size_t)p->batch * p->channels * p->height * p->width * es);
@@ -1477,6 +1479,8 @@ extern "C" int s2a_deform_conv_forward(const void* input, const void* weight, co
   S2A_CHECK_ARG(p.height >= p.kH && p.width >= p.kW, "input image is smaller than kernel");
   if (p.batch == 0) return S2A_OK;
   S2A_CHECK_ARG(input && weight && offset && output, "deform_conv: NULL tensor");
+  // (one rule for both paths: the generic kernel needs no scratch, a caller of the header does not know which path runs)
+  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, s2a_deform_conv_workspace_bytes(pp), "deform_conv_forward");
   hipStream_t st = as_stream(stream);
   if (fast_path_ok(p)) {
     if (p.dtype == S2A_DTYPE_F32)
@@ -1534,7 +1538,9 @@ extern "C" int s2a_modulated_deform_conv_forward(const void* input, const void* 
 }
 
 extern "C" size_t s2a_align_conv_workspace_bytes(const s2a_align_params* p) {
-  if (!p) return 0;
+  if (!p || p->batch < 0 || p->channels <= 0 || p->out_channels <= 0 || p->height < 3 || p->width < 3 ||
+      (p->dtype != S2A_DTYPE_F32 && p->dtype != S2A_DTYPE_F16))
+    return 0;   // (parameters the entry point refuses)
   size_t es = esize(p->dtype);
   size_t b = align_up((size_t)p->out_channels * p->channels * 9 * es * 3) + 256;      // packed filter: f16 two layouts, f32 2.5 x
   if (p->layout == S2A_LAYOUT_NCHW) b += align_up((size_t)p->batch * p->channels * p->height * p->width * es);
@@ -1555,6 +1561,7 @@ extern "C" int s2a_align_conv_forward(const void* x, const float* anchors, const
   S2A_CHECK_ARG(p.batch * p.height * p.width < (1ll << 31), "align_conv: too many positions");
   if (p.batch == 0) return S2A_OK;
   S2A_CHECK_ARG(x && anchors && weight && out, "align_conv: NULL tensor");
+  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, s2a_align_conv_workspace_bytes(pp), "align_conv_forward");
   hipStream_t st = as_stream(stream);
   if (p.dtype == S2A_DTYPE_F32)
     return run_fast<float>(x, anchors, true, weight, out, p.batch, (int)p.channels, (int)p.height,

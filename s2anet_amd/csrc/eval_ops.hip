@@ -502,7 +502,9 @@ int bits_for(uint64_t max_value) {
 using namespace s2a;
 
 extern "C" size_t s2a_eval_task1_workspace_bytes(int64_t num_dets, int64_t num_gts, int32_t num_classes, int32_t num_images) {
-  if (num_dets < 0 || num_gts < 0 || num_classes < 1 || num_images < 1) return 256;
+  if (num_dets < 0 || num_gts < 0 || num_dets >= (1ll << 31) || num_gts >= (1ll << 31) || num_classes < 1 ||
+      num_classes > kEvalMaxClasses || num_images < 1 || ((int64_t)num_classes + 1) * num_images >= (1ll << 31))
+    return 0;   // (sizes the entry point refuses)
   const size_t D = (size_t)num_dets, G = (size_t)num_gts, groups = (size_t)num_classes * (size_t)num_images;
   const size_t nb = (D + kEvalScanTile - 1) / kEvalScanTile;
   return align_up(D * 8) * 2 + align_up(D * 4) * 9 + align_up(D * 8) * 2 + align_up(D) + align_up(nb * 8) + align_up(G * 4) * 5 +
@@ -530,6 +532,7 @@ extern "C" int s2a_eval_task1(const double* det_polys, const double* det_scores,
   const size_t szD = (size_t)D, szG = (size_t)G, groups = (size_t)C * (size_t)I;
   const size_t nb = (szD + kEvalScanTile - 1) / kEvalScanTile;
   hipStream_t st = as_stream(stream);
+  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, s2a_eval_task1_workspace_bytes(D, G, C, I), "eval_task1");
   Carver cv(workspace, workspace_bytes);
   auto* key_a = cv.take<unsigned long long>(szD);
   auto* key_s = cv.take<unsigned long long>(szD);
@@ -568,21 +571,33 @@ extern "C" int s2a_eval_task1(const double* det_polys, const double* det_scores,
     const unsigned gd = (unsigned)((D + 255) / 256);
     k_eval_det_keys<<<gd, 256, 0, st>>>(det_scores, det_labels, det_image, D, C, I, key_a, idx_a);
     S2A_HIP(rocprim::radix_sort_pairs(nullptr, need, key_a, key_s, idx_a, ord1, szD, 0, 64, st));
-    S2A_CHECK_ARG(need <= rpb, "eval_task1: sort scratch too small");
+    if (need > rpb) {
+      set_error("eval_task1: workspace too small (sort scratch %zu < %zu bytes)", rpb, need);
+      return S2A_EWORKSPACE;
+    }
     S2A_HIP(rocprim::radix_sort_pairs(rp, need, key_a, key_s, idx_a, ord1, szD, 0, 64, st));
     k_eval_class_keys<<<gd, 256, 0, st>>>(ord1, det_labels, det_image, D, C, I, ckey_a);
     S2A_HIP(rocprim::radix_sort_pairs(nullptr, need, ckey_a, ckey_s, ord1, order, szD, 0, cbits, st));
-    S2A_CHECK_ARG(need <= rpb, "eval_task1: sort scratch too small");
+    if (need > rpb) {
+      set_error("eval_task1: workspace too small (sort scratch %zu < %zu bytes)", rpb, need);
+      return S2A_EWORKSPACE;
+    }
     S2A_HIP(rocprim::radix_sort_pairs(rp, need, ckey_a, ckey_s, ord1, order, szD, 0, cbits, st));
     k_eval_group_keys<<<gd, 256, 0, st>>>(ckey_s, order, det_image, D, C, I, gkey_a, rank_a);
     S2A_HIP(rocprim::radix_sort_pairs(nullptr, need, gkey_a, gkey_s, rank_a, grp_rank, szD, 0, gbits, st));
-    S2A_CHECK_ARG(need <= rpb, "eval_task1: sort scratch too small");
+    if (need > rpb) {
+      set_error("eval_task1: workspace too small (sort scratch %zu < %zu bytes)", rpb, need);
+      return S2A_EWORKSPACE;
+    }
     S2A_HIP(rocprim::radix_sort_pairs(rp, need, gkey_a, gkey_s, rank_a, grp_rank, szD, 0, gbits, st));
   }
   if (G > 0) {
     k_eval_gt_keys<<<(unsigned)((G + 255) / 256), 256, 0, st>>>(gt_labels, gt_image, G, C, I, gtkey_a, gtidx_a);
     S2A_HIP(rocprim::radix_sort_pairs(nullptr, need, gtkey_a, gtkey_s, gtidx_a, gt_order, szG, 0, gbits, st));
-    S2A_CHECK_ARG(need <= rpb, "eval_task1: sort scratch too small");
+    if (need > rpb) {
+      set_error("eval_task1: workspace too small (sort scratch %zu < %zu bytes)", rpb, need);
+      return S2A_EWORKSPACE;
+    }
     S2A_HIP(rocprim::radix_sort_pairs(rp, need, gtkey_a, gtkey_s, gtidx_a, gt_order, szG, 0, gbits, st));
   }
   const int64_t table_n = std::max<int64_t>((int64_t)groups + 1, G);

@@ -241,11 +241,7 @@ extern "C" int s2a_s2anet_loss_forward(const s2a_loss_params* params, const int6
   }
   const int64_t A = a.level_start[p.n_levels];
   S2A_CHECK_ARG(assign_ids && target_offsets && loss && items && norm, "s2anet_loss: NULL tensor");
-  const size_t need = s2a_s2anet_loss_workspace_bytes(p.batch, A);
-  if (workspace == nullptr || workspace_bytes < need) {
-    set_error("s2anet_loss: workspace %zu < %zu bytes", workspace_bytes, need);
-    return S2A_EWORKSPACE;
-  }
+  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, s2a_s2anet_loss_workspace_bytes(p.batch, A), "s2anet_loss_forward");
   hipStream_t st = as_stream(stream);
   const int64_t nbx = blocks_x(A);
   double* partial = static_cast<double*>(workspace);

@@ -311,14 +311,16 @@ extern "C" int s2a_train_update(const s2a_train_update_args* args, void* workspa
                 "s2a_train_update: skip flag must be int32 or int64 (skip_elem_bytes 4 or 8, got %d)", a.skip_elem_bytes);
   S2A_CHECK_ARG(!a.scaling_enabled || a.growth_interval > 0, "s2a_train_update: growth_interval must be positive");
   S2A_CHECK_ARG(a.ema_tau > 0.0, "s2a_train_update: ema_tau must be positive");
-  const size_t need = s2a_train_update_workspace_bytes(a.n_trained_chunks);
-  S2A_CHECK_ARG(workspace != nullptr && workspace_bytes >= need, "s2a_train_update: workspace too small (%zu < %zu bytes)",
-                workspace_bytes, need);
+  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, s2a_train_update_workspace_bytes(a.n_trained_chunks), "s2a_train_update");
   S2A_CHECK_ARG(((uintptr_t)workspace & 15u) == 0, "s2a_train_update: workspace must be 16-byte aligned");
   Carver ws(workspace, workspace_bytes);
   Ctrl* ctrl = ws.take<Ctrl>(1);
   float* partial = ws.take<float>((size_t)a.n_trained_chunks);
   uint32_t* flags = ws.take<uint32_t>((size_t)a.n_trained_chunks);
+  if (!ctrl || !partial || !flags) {   // (the query and the carving above disagree: never launch on a NULL sub-buffer)
+    set_error("s2a_train_update: workspace too small (%zu < %zu bytes)", workspace_bytes, ws.off);
+    return S2A_EWORKSPACE;
+  }
   hipStream_t st = as_stream(stream);
 
   const bool need_norm = (a.max_norm > 0.0f || a.scaling_enabled) && a.n_trained_chunks > 0;

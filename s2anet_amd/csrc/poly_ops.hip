@@ -560,7 +560,8 @@ static size_t poly_pair_cap(int64_t n) {
 }
 
 extern "C" size_t s2a_nms_poly_workspace_bytes(int64_t n) {
-  if (n <= 0) return 256;
+  if (n < 0 || n >= (1ll << 31)) return 0;   // (sizes the entry point refuses)
+  if (n == 0) return 256;
   size_t sz = (size_t)n, nb = (sz + 63) / 64;
   return align_up(sz * 8) * 2 + align_up(sz * 4) * 2 + align_up(sz * sizeof(PolyBox)) + align_up(sz * nb * 8) +
          align_up(sz) * 2 + align_up(sz * 40 + (8u << 20)) + align_up(poly_pair_cap(n) * 8) * 3 +
@@ -581,6 +582,7 @@ extern "C" int s2a_nms_poly(const double* dets9, int64_t n, double thresh, int64
   S2A_CHECK_ARG(dets9 && keep, "nms_poly: NULL tensor");
   const size_t sz = (size_t)n, nb = (sz + 63) / 64;
   S2A_CHECK_ARG(nb <= 65535, "nms_poly: more than 4.19 M boxes is not supported");
+  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, s2a_nms_poly_workspace_bytes(n), "nms_poly");
   Carver cv(workspace, workspace_bytes);
   auto* key_a = cv.take<unsigned long long>(sz);
   auto* key_b = cv.take<unsigned long long>(sz);
@@ -615,7 +617,10 @@ extern "C" int s2a_nms_poly(const double* dets9, int64_t n, double thresh, int64
   k_poly_keys<<<g, 256, 0, st>>>(dets9, n, key_a, idx_a);
   size_t need = 0;
   S2A_HIP(rocprim::radix_sort_pairs(nullptr, need, key_a, key_b, idx_a, order, sz, 0, 64, st));
-  S2A_CHECK_ARG(need <= rpb, "nms_poly: sort scratch too small");
+  if (need > rpb) {
+    set_error("nms_poly: workspace too small (sort scratch %zu < %zu bytes)", rpb, need);
+    return S2A_EWORKSPACE;
+  }
   S2A_HIP(rocprim::radix_sort_pairs(rp, need, key_a, key_b, idx_a, order, sz, 0, 64, st));
   k_poly_prep<<<g, 256, 0, st>>>(dets9, order, n, sorted, seg_start, num_seg, mask_off, nblk);
   dim3 grid((unsigned)nb, (unsigned)nb);
@@ -662,7 +667,10 @@ extern "C" int s2a_nms_poly(const double* dets9, int64_t n, double thresh, int64
   k_poly_flags<<<g, 256, 0, st>>>(keep_orig, order, n, flags);
   need = 0;
   S2A_HIP(rocprim::select(nullptr, need, order, flags, keep, count_dev, sz, st));
-  S2A_CHECK_ARG(need <= rpb, "nms_poly: select scratch too small");
+  if (need > rpb) {
+    set_error("nms_poly: workspace too small (select scratch %zu < %zu bytes)", rpb, need);
+    return S2A_EWORKSPACE;
+  }
   S2A_HIP(rocprim::select(rp, need, order, flags, keep, count_dev, sz, st));
   S2A_LAUNCH_CHECK();
   if (host_count) {
@@ -673,7 +681,8 @@ extern "C" int s2a_nms_poly(const double* dets9, int64_t n, double thresh, int64
 }
 
 extern "C" size_t s2a_nms_rotated_f64_workspace_bytes(int64_t n) {
-  if (n <= 0) return 256;
+  if (n < 0 || n >= (1ll << 31)) return 0;   // (sizes the entry point refuses)
+  if (n == 0) return 256;
   size_t sz = (size_t)n, nb = (sz + 63) / 64;
   return align_up(sz * 8) * 2 + align_up(sz * 4) * 2 + align_up(sz * sizeof(RBox6)) + align_up(sz * nb * 8) +
          align_up(sz) * 2 + align_up(sz * 40 + (8u << 20)) + 8192;
@@ -694,6 +703,7 @@ extern "C" int s2a_nms_rotated_f64(const double* dets5, const double* scores, co
   S2A_CHECK_ARG(dets5 && scores && keep, "nms_rotated_f64: NULL tensor");
   const size_t sz = (size_t)n, nb = (sz + 63) / 64;
   S2A_CHECK_ARG(nb <= 65535 && sz * nb * 8 < (8ull << 30), "nms_rotated_f64: more than 260 k boxes is not supported (N x N/64 mask)");
+  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, s2a_nms_rotated_f64_workspace_bytes(n), "nms_rotated_f64");
   Carver cv(workspace, workspace_bytes);
   auto* key_a = cv.take<unsigned long long>(sz);
   auto* key_b = cv.take<unsigned long long>(sz);
@@ -721,7 +731,10 @@ extern "C" int s2a_nms_rotated_f64(const double* dets5, const double* scores, co
   k_rot64_keys<<<g, 256, 0, st>>>(scores, n, key_a, idx_a);
   size_t need = 0;
   S2A_HIP(rocprim::radix_sort_pairs(nullptr, need, key_a, key_b, idx_a, order, sz, 0, 64, st));
-  S2A_CHECK_ARG(need <= rpb, "nms_rotated_f64: sort scratch too small");
+  if (need > rpb) {
+    set_error("nms_rotated_f64: workspace too small (sort scratch %zu < %zu bytes)", rpb, need);
+    return S2A_EWORKSPACE;
+  }
   S2A_HIP(rocprim::radix_sort_pairs(rp, need, key_a, key_b, idx_a, order, sz, 0, 64, st));
   k_rot64_prep<<<g, 256, 0, st>>>(dets5, labels, order, n, sorted, seg_start, num_seg, mask_off, nblk);
   k_rot64_mask<<<dim3((unsigned)nb, (unsigned)nb), 64, 0, st>>>(sorted, n, iou_threshold, mask);
@@ -732,7 +745,10 @@ extern "C" int s2a_nms_rotated_f64(const double* dets5, const double* scores, co
   k_poly_flags<<<g, 256, 0, st>>>(keep_orig, order, n, flags);
   need = 0;
   S2A_HIP(rocprim::select(nullptr, need, order, flags, keep, count_dev, sz, st));
-  S2A_CHECK_ARG(need <= rpb, "nms_rotated_f64: select scratch too small");
+  if (need > rpb) {
+    set_error("nms_rotated_f64: workspace too small (select scratch %zu < %zu bytes)", rpb, need);
+    return S2A_EWORKSPACE;
+  }
   S2A_HIP(rocprim::select(rp, need, order, flags, keep, count_dev, sz, st));
   S2A_LAUNCH_CHECK();
   if (host_count) {

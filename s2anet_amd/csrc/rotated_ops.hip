@@ -3046,6 +3046,7 @@ struct NmsPlan {
   unsigned long long queue_cap;   // pair list (cull survivors)
   unsigned long long edge_cap;    // edges (pairs above the threshold)
   unsigned long long tile_cap;    // tiles that pass the bounding-box filter
+  bool closed_form;               // rocprim_bytes is the bound of a host without a device, not the library's answer
 };
 
 struct NmsBuffers {
@@ -3083,6 +3084,7 @@ int nms_plan(int64_t n, int64_t max_seg_rows, NmsPlan* plan) {
     a = sz * 32 + (8u << 20);
   }
   plan->rocprim_bytes = a;
+  plan->closed_form = !ok;
   // pair list: all same-segment pairs when small, else 16 Mi entries + 256/row
   unsigned long long all_pairs = (unsigned long long)n * (unsigned long long)max_seg_rows / 2 + 64;
   unsigned long long want = (16ull << 20) + 256ull * (unsigned long long)n;
@@ -3346,7 +3348,8 @@ int nms_core(const float* dets, const float* scores, const float* labels, const 
 }
 
 size_t nms_workspace_bytes(int64_t n, int64_t max_seg_rows) {
-  if (n <= 0) return 256;
+  if (n < 0 || n >= (1ll << 31)) return 0;   // (sizes the entry points refuse)
+  if (n == 0) return 256;
   NmsPlan pl;
   if (nms_plan(n, max_seg_rows, &pl) != 0) return 0;
   Carver cv(nullptr, 0);
@@ -3354,6 +3357,25 @@ size_t nms_workspace_bytes(int64_t n, int64_t max_seg_rows) {
   nms_carve(cv, n, pl, &B);
   // (+ 64 KB: the segmented entry points want 48 KB of lists behind the fixed part, which the plan of a tiny n does not reach)
   return cv.off + 256 + (64u << 10);
+}
+
+// what an NMS entry point checks its workspace against.  whole: the drop-in forms carve their lists for n rows in ONE segment,
+// nms_workspace_bytes(n, n); else the segmented forms, which split whatever lies behind the fixed part over their lists and
+// are not told the max_segment_rows the caller sized for: the smallest declaration, nms_workspace_bytes(n, 1).  One
+// remembered answer per thread and form: the launch-paced small path repeats one n, and the plan behind the number asks the
+// sort library for its scratch size.
+size_t nms_checked_workspace(int64_t n, bool whole) {
+  static thread_local int64_t last_n[2] = {-1, -1};
+  static thread_local size_t last_need[2] = {0, 0};
+  const int k = whole ? 1 : 0;
+  if (n == last_n[k]) return last_need[k];
+  const size_t need = nms_workspace_bytes(n, whole ? n : 1);
+  NmsPlan pl;
+  if (nms_plan(n, 1, &pl) == 0 && !pl.closed_form) {   // (the bound of a device-less host is not remembered)
+    last_n[k] = n;
+    last_need[k] = need;
+  }
+  return need;
 }
 
 #ifdef S2A_MEASURE
@@ -3420,7 +3442,7 @@ void small_slot_release(int device, int slot, bool taken, bool count = true) {
 
 int nms_dropin(const float* dets, const float* scores, const float* labels, int64_t n, float thr,
                int64_t* keep, int64_t* count_dev, int64_t* host_count, void* ws, size_t ws_bytes,
-               hipStream_t st) {
+               hipStream_t st, const char* who) {
   S2A_CHECK_ARG(n >= 0 && n < (1ll << 31), "nms_rotated: n out of range");
   S2A_CHECK_ARG(count_dev != nullptr, "nms_rotated: count_dev must not be NULL");
   if (n == 0) {
@@ -3429,6 +3451,7 @@ int nms_dropin(const float* dets, const float* scores, const float* labels, int6
     return S2A_OK;
   }
   S2A_CHECK_ARG(dets && scores && keep, "nms_rotated: NULL tensor");
+  S2A_CHECK_WORKSPACE(ws, ws_bytes, nms_checked_workspace(n, true), who);
   // small synchronous calls: ONE launch (k_nms_small); anything outside its limits reports a status and falls through to
   // the general path below.  S2A_NMS_SMALL=0: A/B, tests
   {
@@ -3592,7 +3615,10 @@ int launch_nms_edge_rounds(uint2* edges, unsigned long long edge_cap, const unsi
   auto* W = cv.take<EdgeRoundsWs>(1);
   auto* state = cv.take<uint8_t>((size_t)n);
   auto* blocked = cv.take<uint8_t>(2 * (size_t)n);
-  S2A_CHECK_ARG(W && state && blocked, "nms edge rounds: workspace too small");
+  if (!W || !state || !blocked) {
+    set_error("nms edge rounds: workspace too small (%zu < %zu bytes)", workspace_bytes, cv.off);
+    return S2A_EWORKSPACE;
+  }
   k_edge_rounds_init<<<grid_for(n), 256, 0, st>>>(W, state, blocked, n, edge_count_dev);
   for (int r = 1; r <= kNmsRounds; r++)
     k_nms_round<<<256, kThreads, 0, st>>>(edges, &W->C, edge_cap, state, blocked, n, r, r == kNmsRounds ? alive_list : nullptr, alive_cap);
@@ -3632,7 +3658,8 @@ int launch_nms_scan(const unsigned long long* mask, const uint32_t* seg_start, c
 using namespace s2a;
 
 extern "C" size_t s2a_box_iou_rotated_workspace_bytes(int64_t n, int64_t m) {
-  if (n <= 0 || m <= 0) return 256;
+  if (n < 0 || m < 0 || n >= (1ll << 31) || m >= (1ll << 31)) return 0;   // (sizes the entry point refuses)
+  if (n == 0 || m == 0) return 256;
   unsigned long long pairs = (unsigned long long)n * (unsigned long long)m;
   unsigned long long cap = std::max<unsigned long long>(std::min<unsigned long long>(pairs, kIouQueueCap), (unsigned long long)m * 256);
   return align_up((size_t)(n + m) * sizeof(PreBox)) * 2 + align_up(cap * (sizeof(uint2) + sizeof(float))) + 8192;
@@ -3651,6 +3678,7 @@ extern "C" int s2a_box_iou_rotated(const float* boxes1, int64_t n, const float* 
   if (n == 0 || m == 0) return S2A_OK;  // reference: empty [N,M] (cuda.cu:79)
   S2A_CHECK_ARG(boxes1 && boxes2 && ious, "box_iou_rotated: NULL tensor");
   S2A_CHECK_ARG(n < (1ll << 31) && m < (1ll << 31), "box_iou_rotated: size out of range");
+  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, s2a_box_iou_rotated_workspace_bytes(n, m), "box_iou_rotated");
   hipStream_t st = as_stream(stream);
   Carver cv(workspace, workspace_bytes);
   PreBox* P1 = cv.take<PreBox>((size_t)n);
@@ -3670,7 +3698,10 @@ extern "C" int s2a_box_iou_rotated(const float* boxes1, int64_t n, const float* 
   int64_t rows_per_chunk = (int64_t)std::min<unsigned long long>((unsigned long long)n, 4 * (cap / (unsigned long long)m));
   if (rows_per_chunk < n) rows_per_chunk = std::max<int64_t>(256, rows_per_chunk / 256 * 256);   // (else: one chunk)
   int64_t chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
-  S2A_CHECK_ARG(chunks <= 512, "box_iou_rotated: workspace too small for %lld x %lld", (long long)n, (long long)m);
+  if (chunks > 512) {
+    set_error("box_iou_rotated: workspace too small for %lld x %lld", (long long)n, (long long)m);
+    return S2A_EWORKSPACE;
+  }
   // Large outputs are write-bound (4 B per pair, ~1 % of DOTA-like pairs overlap): the zero-fill of the whole matrix
   // runs on a side stream at the full store rate while this stream finds the overlapping pairs and evaluates them into a
   // compact buffer; after the join a small kernel drops the values into place.  (Round 1 stored the zeros from the cull
@@ -3984,6 +4015,7 @@ __global__ void k_assign_empty(const float* __restrict__ anchors, int64_t M, flo
 }  // namespace s2a
 
 extern "C" size_t s2a_assign_labels_workspace_bytes(int64_t num_anchors, int64_t num_gts) {
+  if (num_anchors < 0 || num_gts < 0 || num_anchors >= (1ll << 31) || num_gts >= (1ll << 31)) return 0;   // (refused sizes)
   const int64_t M = std::max<int64_t>(num_anchors, 1), N = std::max<int64_t>(num_gts, 1);
   const size_t matrix_form = align_up((size_t)M * N * 4) + 2 * align_up((size_t)N * 4) + s2a_box_iou_rotated_workspace_bytes(M, N) + 1024;
   const size_t list_form = align_up((size_t)N * 32) + 2 * align_up((size_t)N * 4) + align_up((size_t)M * 8) + 2 * align_up((size_t)M * 4) +
@@ -4006,6 +4038,7 @@ extern "C" int s2a_assign_labels(const float* anchors, int64_t num_anchors, cons
     S2A_LAUNCH_CHECK();
     return S2A_OK;
   }
+  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, s2a_assign_labels_workspace_bytes(M, N), "assign_labels");
   // list form: no IoU matrix, five short launches (see k_assign_cull).  S2A_ASSIGN_LIST=0: the matrix form (A/B, tests)
   {
     const char* e = std::getenv("S2A_ASSIGN_LIST");
@@ -4193,6 +4226,7 @@ __global__ void k_gather_candidates(const float* __restrict__ boxes5, const floa
 }  // namespace s2a
 
 extern "C" size_t s2a_multiclass_candidates_workspace_bytes(int64_t total) {
+  if (total < 0 || total >= (1ll << 31)) return 0;   // (sizes the entry point refuses)
   const size_t t = (size_t)std::max<int64_t>(total, 1);
   return align_up(t * 4) + align_up(((t + kCandBlock - 1) / kCandBlock + 1) * 4) + 1024;
 }
@@ -4214,6 +4248,7 @@ extern "C" int s2a_multiclass_candidates(const float* boxes, const float* scores
     return S2A_OK;
   }
   S2A_CHECK_ARG(boxes && scores, "multiclass_candidates: NULL input");
+  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, s2a_multiclass_candidates_workspace_bytes(total), "multiclass_candidates");
   Carver cv(workspace, workspace_bytes);
   const int64_t nb = (total + kCandBlock - 1) / kCandBlock;
   int32_t* sel = cv.take<int32_t>((size_t)total);
@@ -4255,14 +4290,14 @@ extern "C" int s2a_ml_nms_rotated(const float* dets, const float* scores, const 
                                   int64_t* host_count, void* workspace, size_t workspace_bytes,
                                   s2a_stream_t stream) {
   return nms_dropin(dets, scores, labels, n, iou_threshold, keep, count_dev, host_count, workspace,
-                    workspace_bytes, as_stream(stream));
+                    workspace_bytes, as_stream(stream), "ml_nms_rotated");
 }
 
 extern "C" int s2a_nms_rotated(const float* dets, const float* scores, int64_t n, float iou_threshold,
                                int64_t* keep, int64_t* count_dev, int64_t* host_count,
                                void* workspace, size_t workspace_bytes, s2a_stream_t stream) {
   return nms_dropin(dets, scores, nullptr, n, iou_threshold, keep, count_dev, host_count, workspace,
-                    workspace_bytes, as_stream(stream));
+                    workspace_bytes, as_stream(stream), "nms_rotated");
 }
 
 namespace {
@@ -4303,7 +4338,7 @@ __global__ __launch_bounds__(256) void k_nms_emit_empty(int32_t num_groups, int3
 int nms_segmented_impl(const float* dets, const float* scores, const int32_t* segment_ids, const int32_t* group_ids,
                        int64_t n, int32_t num_segments, int32_t num_groups, float iou_threshold, uint8_t* keep_flags,
                        int32_t* keep, int32_t* group_counts, int32_t max_per_group, const NmsEmit& em, void* workspace,
-                       size_t workspace_bytes, hipStream_t st) {
+                       size_t workspace_bytes, hipStream_t st, const char* who) {
   S2A_CHECK_ARG(n >= 0 && n < (1ll << 31), "nms_rotated_segmented: n out of range");
   S2A_CHECK_ARG(num_segments > 0 && num_groups > 0, "nms_rotated_segmented: bad segment/group count");
   S2A_CHECK_ARG(keep == nullptr || (group_counts != nullptr && max_per_group > 0),
@@ -4325,6 +4360,8 @@ int nms_segmented_impl(const float* dets, const float* scores, const int32_t* se
   }
   S2A_CHECK_ARG(dets && scores && segment_ids, "nms_rotated_segmented: NULL tensor");
   S2A_CHECK_ARG(em.wire == nullptr || em.row_labels != nullptr, "nms_rotated_segmented_dets: the detection rows need row_labels");
+  // (the smallest declaration: a caller sizes with the largest segment it can promise, which the call does not learn)
+  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, nms_checked_workspace(n, false), who);
   NmsPlan pl;
   S2A_CHECK_ARG(nms_plan(n, n, &pl) == 0, "nms_rotated_segmented: rocprim size query failed");
   // the caller may have sized the workspace with a tighter per-segment bound (s2a_nms_rotated_workspace_bytes(n,
@@ -4340,14 +4377,21 @@ int nms_segmented_impl(const float* dets, const float* scores, const int32_t* se
   }
   size_t rest = (workspace_bytes - cv.off) / 256 * 256;
   char* base = static_cast<char*>(workspace) + cv.off;
+  // the plan of a few rows asks for fewer entries than the floors below (n = 1: 3 tiles, 64 pairs): the 48 KB behind the
+  // fixed part always hold the floors, so ask for at least them (up to 43 rows were refused whatever the workspace)
+  pl.tile_cap = std::max<unsigned long long>(pl.tile_cap, 64);
+  pl.edge_cap = std::max<unsigned long long>(pl.edge_cap, 1024);
+  pl.queue_cap = std::max<unsigned long long>(pl.queue_cap, 1024);
   const size_t tbytes = std::min((size_t)pl.tile_cap * sizeof(TileRef), rest / 6) / 256 * 256;
   const size_t ebytes = std::min((size_t)pl.edge_cap * sizeof(uint2), (rest - tbytes) / 3) / 256 * 256;
   const size_t qbytes = std::min((size_t)pl.queue_cap * sizeof(uint2), rest - tbytes - ebytes) / 256 * 256;
   pl.tile_cap = tbytes / sizeof(TileRef);
   pl.edge_cap = ebytes / sizeof(uint2);
   pl.queue_cap = qbytes / sizeof(uint2);
-  S2A_CHECK_ARG(pl.tile_cap >= 64 && pl.edge_cap >= 1024 && pl.queue_cap >= 1024,
-                "nms_rotated_segmented: workspace too small for the pair / edge / tile lists");
+  if (!(pl.tile_cap >= 64 && pl.edge_cap >= 1024 && pl.queue_cap >= 1024)) {
+    set_error("%s: workspace too small for the pair / edge / tile lists (%zu bytes)", who, workspace_bytes);
+    return S2A_EWORKSPACE;
+  }
   B.tiles = reinterpret_cast<TileRef*>(base);
   B.edges = reinterpret_cast<uint2*>(base + tbytes);
   B.gq = reinterpret_cast<uint2*>(base + tbytes + ebytes);
@@ -4395,7 +4439,7 @@ extern "C" int s2a_nms_rotated_segmented(const float* dets, const float* scores,
                                          s2a_stream_t stream) {
   return nms_segmented_impl(dets, scores, segment_ids, group_ids, n, num_segments, num_groups, iou_threshold, keep_flags,
                             keep, group_counts, max_per_group, NmsEmit{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, workspace,
-                            workspace_bytes, as_stream(stream));
+                            workspace_bytes, as_stream(stream), "nms_rotated_segmented");
 }
 
 extern "C" int s2a_nms_rotated_segmented_dets(const float* dets, const float* scores, const int32_t* segment_ids,
@@ -4408,5 +4452,5 @@ extern "C" int s2a_nms_rotated_segmented_dets(const float* dets, const float* sc
   S2A_CHECK_ARG(wire != nullptr, "nms_rotated_segmented_dets: NULL output");
   return nms_segmented_impl(dets, scores, segment_ids, group_ids, n, num_segments, num_groups, iou_threshold, nullptr,
                             nullptr, nullptr, max_per_group, NmsEmit{row_labels, wire, labels_out, counts_out, cand_found, overflow_out, dropped_total}, workspace,
-                            workspace_bytes, as_stream(stream));
+                            workspace_bytes, as_stream(stream), "nms_rotated_segmented_dets");
 }

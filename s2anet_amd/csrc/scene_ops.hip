@@ -356,7 +356,8 @@ extern "C" int s2a_scene_gather_u8(const uint8_t* scene, int64_t height, int64_t
 }
 
 extern "C" size_t s2a_scene_merge_workspace_bytes(int64_t n_rows, int64_t pair_capacity) {
-  if (n_rows <= 0) return 256;
+  if (n_rows < 0 || n_rows >= (1ll << 31)) return 0;   // (sizes the entry point refuses)
+  if (n_rows == 0) return 256;
   const size_t sz = (size_t)n_rows, cap = scene_pair_cap(n_rows, pair_capacity);
   return align_up(sz * 8) * 2 + align_up(sz * 4) * 2 + align_up(sz * 32) + align_up(sz * sizeof(PolyBox)) + align_up(sz) +
          align_up(sizeof(MergeCtl)) + align_up((kMaxClasses + 2) * 4) + align_up(((sz + kOutRows - 1) / kOutRows) * 4) +
@@ -381,6 +382,7 @@ extern "C" int s2a_scene_merge(const float* dets, const int32_t* labels, const i
     return S2A_OK;
   }
   S2A_CHECK_ARG(dets && labels && counts && origins && out_polys && out_scores && out_labels && out_src, "scene_merge: NULL tensor");
+  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, s2a_scene_merge_workspace_bytes(n, pair_capacity), "scene_merge");
   const size_t sz = (size_t)n, cap = scene_pair_cap(n, pair_capacity);
   const int nb = (int)((sz + kOutRows - 1) / kOutRows);
   Carver cv(workspace, workspace_bytes);
@@ -411,7 +413,10 @@ extern "C" int s2a_scene_merge(const float* dets, const int32_t* labels, const i
                                   reinterpret_cast<long long*>(class_counts));
   size_t need = 0;
   S2A_HIP(rocprim::radix_sort_pairs(nullptr, need, key_a, key_s, idx_a, order, sz, 0, 48, st));
-  S2A_CHECK_ARG(need <= rpb, "scene_merge: sort scratch too small");
+  if (need > rpb) {
+    set_error("scene_merge: workspace too small (sort scratch %zu < %zu bytes)", rpb, need);
+    return S2A_EWORKSPACE;
+  }
   S2A_HIP(rocprim::radix_sort_pairs(rp, need, key_a, key_s, idx_a, order, sz, 0, 48, st));
   int rc = s2a_rbox_to_poly(dets, n, 6, polys32, stream);
   if (rc != S2A_OK) return rc;
