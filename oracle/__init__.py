@@ -513,7 +513,7 @@ def delta2bbox_rotated(rois, deltas, wh_ratio_clip=16 / 1000):
 def deform_conv_backward(x, offset, weight, grad_out, stride=(1, 1), padding=(1, 1), dilation=(1, 1),
                          deformable_groups=1):
     """deform_conv_backward_input_cuda + _parameters_cuda restated (groups = 1):
-    -> (grad_input, grad_offset, grad_weight), float32"""
+    -> (grad_input, grad_offset, grad_weight), float32.  Grouped cases: oracle/dcn64_general.py (float64, any geometry)"""
     x, offset, weight, grad_out = _f32(x), _f32(offset), _f32(weight), _f32(grad_out)
     B, C, H, W = x.shape
     O, _, kH, kW = weight.shape

@@ -90,11 +90,15 @@ template <typename A = float>
 __device__ __forceinline__ A gradient_weight(A ah, A aw, int h, int w, int H, int W) {
   if (ah <= -1 || ah >= H || aw <= -1 || aw >= W) return (A)0;
   int hl = (int)floor(ah), wl = (int)floor(aw), hh = hl + 1, wh = wl + 1;
+  // the fractions first (exact differences), as bilinear_at and k_def_col2im_tiled form them: the reference's (ah + 1 - h)
+  // rounds its first addition at the size of the coordinate, an absolute error of u * (|ah| + 1) on a weight that can be
+  // arbitrarily small (4e-5 relative on a weight of 0.012 at row 8 in f32)
+  const A lh = ah - hl, lw = aw - wl;
   A weight = 0;
-  if (h == hl && w == wl) weight = (h + 1 - ah) * (w + 1 - aw);
-  if (h == hl && w == wh) weight = (h + 1 - ah) * (aw + 1 - w);
-  if (h == hh && w == wl) weight = (ah + 1 - h) * (w + 1 - aw);
-  if (h == hh && w == wh) weight = (ah + 1 - h) * (aw + 1 - w);
+  if (h == hl && w == wl) weight = (1 - lh) * (1 - lw);
+  if (h == hl && w == wh) weight = (1 - lh) * lw;
+  if (h == hh && w == wl) weight = lh * (1 - lw);
+  if (h == hh && w == wh) weight = lh * lw;
   return weight;
 }
 

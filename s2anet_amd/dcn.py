@@ -22,6 +22,16 @@ def _is_nhwc(t):
     return t.dim() == 4 and not t.is_contiguous() and t.is_contiguous(memory_format=torch.channels_last)
 
 
+def _fast_forward_ok(input, weight, offset, kW, kH, dW, dH, padW, padH, dilationW, dilationH, group, deformable_group):
+    """the shapes s2a_deform_conv_forward runs on its fused kernels (fast_path_ok of csrc/dcn_ops.hip): AlignConv geometry,
+    f16 / f32, float32 offsets, C % 64 (f16) / C % 32 (f32), O % 64; everything else takes the generic kernel"""
+    B, C, H, W = input.shape
+    return (input.dtype in (torch.float16, torch.float32) and offset.dtype == torch.float32
+            and (kW, kH, dW, dH, padW, padH, dilationW, dilationH) == (3, 3, 1, 1, 1, 1, 1, 1)
+            and group == 1 and deformable_group == 1 and C % (32 if input.dtype == torch.float32 else 64) == 0
+            and weight.shape[0] % 64 == 0 and B * H * W < (1 << 31))
+
+
 def deform_conv_forward_cuda(input, weight, offset, output, columns, ones, kW, kH, dW, dH, padW,
                              padH, dilationW, dilationH, group, deformable_group, im2col_step,
                              relu=False):
@@ -39,16 +49,20 @@ def deform_conv_forward_cuda(input, weight, offset, output, columns, ones, kW, k
     squeeze = input.dim() == 3
     if squeeze:
         input, offset, output = input.unsqueeze(0), offset.unsqueeze(0), output.unsqueeze(0)
-    nhwc = _is_nhwc(input) and _is_nhwc(output) and input.dtype != torch.float64
+    off = offset.contiguous()
+    if input.dtype == torch.float64:
+        off = off.double()                      # the float64 instantiation takes float64 offsets (deform_conv.py:45 casts them)
+    elif off.dtype not in (torch.float32, input.dtype):
+        off = off.float()
+    # channels-last tensors go to the library as they are only where its fused kernels run (they read NHWC natively); the
+    # generic kernel indexes NCHW, so every other call hands it contiguous copies, as the reference's input.contiguous()
+    # (deform_conv_cuda.cpp:168) does
+    nhwc = (_is_nhwc(input) and _is_nhwc(output) and
+            _fast_forward_ok(input, weight, off, kW, kH, dW, dH, padW, padH, dilationW, dilationH, group, deformable_group))
     x = input if nhwc else input.contiguous()
     w = weight.contiguous()
     if w.dtype != x.dtype:
         w = w.to(x.dtype)
-    off = offset.contiguous()
-    if x.dtype == torch.float64:
-        off = off.double()                      # the float64 instantiation takes float64 offsets (deform_conv.py:45 casts them)
-    elif off.dtype not in (torch.float32, x.dtype):
-        off = off.float()
     B, C, H, W = x.shape
     O = w.shape[0]
     if w.shape[1] * group != C:
