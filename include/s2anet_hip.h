@@ -55,6 +55,29 @@ const char* s2a_last_error(void);
 const char* s2a_version(void);
 
 /* ---------------------------------------------------------------------------
+ * Deterministic training mode: one process-wide atomic flag, off by default; the environment switch S2A_DETERMINISTIC
+ * (anything but empty or "0") sets its initial value.  s2a_set_deterministic returns the previous value.  The flag is read
+ * when a call is ISSUED: a captured graph keeps the mode it was captured in.  Off: nothing anywhere differs.  On:
+ *   * the f16 fused input gradient of the deformable convolution (s2a_deform_conv_backward_typed / s2a_deform_conv_backward
+ *     with S2A_DTYPE_F16, s2a_deform_conv_backward_input_f16) sums into 64-bit FIXED-POINT cells instead of f32 atomics:
+ *     every contribution v enters as rint(v * 2^32) through one 64-bit integer atomic add, so the sum does not depend on the
+ *     order the workgroups arrive in.  Quantum 2^-32 (below 1/256 of the smallest f16 subnormal; n contributions are off
+ *     by at most n * 2^-33; the cell is then read as a double -- exact for |sum| < 2^21 -- and rounded once to f16, or
+ *     added to the f32 gradInput in double and rounded to f32).  Finite range |v| < 2^20
+ *     (sixteen times the f16 maximum); a cell cannot overflow below 2048 contributions of that magnitude (in general while
+ *     the sum of |v| over a cell's contributions stays below 2^31).  A contribution that is NaN, infinite or at / beyond the
+ *     range stays out of the integer sum and is recorded in a sticky class byte per cell: only +inf (or v >= 2^20) seen ->
+ *     +inf, only -inf (or v <= -2^20) -> -inf, anything else -> NaN; a cell no such contribution reached is bit-equal to
+ *     the same call without it.  Cells and class bytes (9 bytes per gradInput element instead of 4) come out of the
+ *     workspace: the *_workspace_bytes queries of these entries answer for the mode that is on when they are called;
+ *   * the f32 fused input gradient (s2a_deform_conv_backward_input_f32, the S2A_DTYPE_F32 forms with a grad_input) and
+ *     s2a_deformable_col2im add floats straight into the caller's tensor and have no deterministic form: they return
+ *     S2A_EINVAL with a message naming the mode, before any launch.  Weight-only calls are unaffected (no atomics).
+ * Scope: bit-equal results from run to run on one device type (the weight gradients' split depends on the CU count). */
+int s2a_set_deterministic(int on);
+int s2a_get_deterministic(void);
+
+/* ---------------------------------------------------------------------------
  * Rotated-box IoU.  Replaces  utils.box_iou_rotated.box_iou_rotated_cuda.box_iou_rotated
  * (utils/box_iou_rotated/src/box_iou_rotated.h:22-42, kernel box_iou_rotated_cuda.cu:14-101).
  * boxes1[N,5], boxes2[M,5] f32 (x_ctr,y_ctr,w,h,angle_rad) -> ious[N,M] f32.

@@ -5,6 +5,7 @@ library ``libs2anet_hip.so`` (include/s2anet_hip.h).  There is NO CPU fallback: 
 raises if the HIP library is missing or a tensor is not on the GPU.
 """
 from . import _lib  # noqa: F401
+from ._lib import deterministic
 from .rotated import (box_iou_rotated, nms_rotated, ml_nms_rotated, multiclass_nms_rotated,
                       batched_multiclass_nms_rotated, assign_labels, assign_labels_batched)
 from .orn import arf_forward, arf_backward, active_rotating_filter, ORConv2d, RotationInvariantPooling
@@ -28,5 +29,5 @@ __all__ = [
     "evaluate_task1", "Task1Evaluator", "Task1Result", "claim_tp_fp",
     "TrainUpdate", "reference_param_groups", "reference_lr",
     "train_kernels", "train_conv_ok", "FusedConv2d", "FusedConvFunction",
-    "quantize_weight_e4m3", "calibrate_fp8", "fp8_towers",
+    "quantize_weight_e4m3", "calibrate_fp8", "fp8_towers", "deterministic",
 ]

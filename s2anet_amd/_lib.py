@@ -98,6 +98,8 @@ class AnchorSet(ctypes.Structure):
 SYMBOLS = {
     "s2a_last_error": (ctypes.c_char_p, []),
     "s2a_version": (ctypes.c_char_p, []),
+    "s2a_set_deterministic": (c_int, [c_int]),
+    "s2a_get_deterministic": (c_int, []),
     "s2a_box_iou_rotated_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "s2a_box_iou_rotated": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
     "s2a_box_iou_rotated_pairs": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp]),
@@ -254,6 +256,33 @@ def lib():
                 "rebuild with `make -C s2anet_amd/csrc` (scripts that build such objects set S2A_ALLOW_MEASURE_BUILD=1)")
         _lib = L
     return _lib
+
+
+class _ModeGuard:
+    """what deterministic(on) returns: the previous value, and a context manager that puts it back"""
+
+    def __init__(self, previous):
+        self.previous = bool(previous)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        lib().s2a_set_deterministic(int(self.previous))
+        return False
+
+    def __repr__(self):
+        return f"<deterministic: was {self.previous}>"
+
+
+def deterministic(on=None):
+    """deterministic training mode of the library (s2a_set_deterministic; initial value: S2A_DETERMINISTIC).
+    deterministic() -> bool, the current value.  deterministic(on) sets it at once and returns a guard holding `.previous`;
+    `with deterministic(True): ...` restores the previous value on the way out, also after an exception.  The flag is read
+    when a call is issued: a captured graph keeps the mode it was captured in."""
+    if on is None:
+        return bool(lib().s2a_get_deterministic())
+    return _ModeGuard(lib().s2a_set_deterministic(int(bool(on))))
 
 
 def check(rc):

@@ -90,7 +90,17 @@ class AlignConvFunction(torch.autograd.Function):
         go = grad_output.masked_fill(out <= 0, 0)
         w = weight.type_as(x)
         one = (1, 1)
-        if _fused_backward_ok(x, offset, w, go, one, one, one, 1, 1):
+        fused = _fused_backward_ok(x, offset, w, go, one, one, one, 1, 1)
+        if _lib.deterministic() and not ctx.needs_input_grad[0] and not (fused and x.dtype == torch.float16):
+            # deterministic mode refuses the routes whose input gradient is a sum of float atomics (everything but the fused
+            # f16 one); a backward that does not want the input gradient takes none of them: the filter's gradient alone
+            gw = None
+            if ctx.needs_input_grad[2]:
+                gw = torch.zeros_like(w)
+                deform_conv_backward_parameters_cuda(x, offset, go, gw, None, None, 3, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, min(64, B))
+                gw = gw.to(weight.dtype)
+            return None, None, gw, None
+        if fused:
             gin, _, gw = _fused_backward(x, offset, w, go)
         else:
             cur = min(64, B)

@@ -1,5 +1,7 @@
 #include "common.hpp"
 
+#include <atomic>
+#include <cstdlib>
 #include <cstring>
 
 namespace s2a {
@@ -11,7 +13,20 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 const char* get_error() { return g_err; }
+
+// one process-wide flag; S2A_DETERMINISTIC (anything but empty / "0") sets its initial value
+static std::atomic<int>& det_flag() {
+  static std::atomic<int> f([] {
+    const char* e = std::getenv("S2A_DETERMINISTIC");
+    return (e && e[0] && !(e[0] == '0' && !e[1])) ? 1 : 0;
+  }());
+  return f;
+}
+bool deterministic() { return det_flag().load(std::memory_order_relaxed) != 0; }
 }  // namespace s2a
+
+extern "C" int s2a_set_deterministic(int on) { return s2a::det_flag().exchange(on ? 1 : 0); }
+extern "C" int s2a_get_deterministic(void) { return s2a::det_flag().load(); }
 
 extern "C" const char* s2a_last_error(void) { return s2a::get_error(); }
 extern "C" const char* s2a_version(void) { return "s2anet_hip 0.1 (gfx950)"; }

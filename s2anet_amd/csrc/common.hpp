@@ -12,6 +12,9 @@ namespace s2a {
 
 void set_error(const char* fmt, ...);
 
+// deterministic training mode (s2a_set_deterministic; initial value: S2A_DETERMINISTIC): read when a call is issued
+bool deterministic();
+
 inline hipStream_t as_stream(s2a_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }

@@ -313,6 +313,83 @@ __global__ __launch_bounds__(256) void k_bwd_acc_to_nchw(const float* __restrict
   }
 }
 
+// ---- deterministic mode (s2a_set_deterministic): the accumulator of the f16 input gradient in 64-bit fixed point.
+// A cell is a signed 64-bit integer counting units of 2^-32 (kFxScale); every contribution v enters as rint(v * 2^32) with one
+// 64-bit integer atomic add, and integer addition is associative: whatever order the workgroups arrive in, the sum has the
+// same bits.  |v| < 2^20 (kFxLimit, sixteen times the f16 maximum) is the finite range: such a contribution is below 2^52
+// units, so a cell cannot overflow below 2^63 / 2^52 = 2048 contributions of the largest magnitude (in general: while the
+// sum of |v| over its contributions stays below 2^31).  A contribution that is NaN, infinite or at / beyond the range never
+// enters the integer sum: it sets a bit of the cell's CLASS byte instead (bit 0: +inf or v >= 2^20, bit 1: -inf or v <= -2^20,
+// bit 2: NaN), with an atomic OR on the 32-bit word that holds four class bytes.  The class bytes follow the cells in one
+// buffer -- [n cells: 8 n bytes][n class bytes] -- so that one fill launch clears both and the kernels find them from the
+// shape alone.  k_bwd_fx_to_nchw resolves a cell: class 0 -> its integer / 2^32 in double (exact while |cell| < 2^53 units,
+// i.e. |sum| < 2^21: thirty-two times the f16 maximum, beyond which the f16 result is infinite anyway), bit 0 alone -> +inf,
+// bit 1 alone -> -inf, anything else -> NaN.  Typed form: one rounding, double -> f16.  Accumulating form: one add to the
+// caller's f32 value in double (which may round at 2^-53 relative), then one rounding to f32.  Both are fixed functions of
+// the cell, so neither costs reproducibility.
+using fx_cell = unsigned long long;
+constexpr float kFxLimit = 1048576.f;            // 2^20
+constexpr double kFxScale = 4294967296.0;        // 2^32
+
+template <typename A>
+__device__ __forceinline__ void bwd_acc_add(A* __restrict__ acc, int64_t n_cells, int64_t idx, float v) {
+  if constexpr (sizeof(A) == 4) {
+    atomicAdd(acc + idx, v);
+  } else {
+    if (__builtin_fabsf(v) < kFxLimit) {         // (false for NaN)
+      const long long q = __double2ll_rn((double)v * kFxScale);
+      if (q != 0) atomicAdd(acc + idx, (fx_cell)q);
+    } else {
+      const unsigned bit = v != v ? 4u : (v > 0.f ? 1u : 2u);
+      atomicOr(reinterpret_cast<unsigned*>(acc + n_cells) + (idx >> 2), bit << (8 * (int)(idx & 3)));
+    }
+  }
+}
+
+// double -> f16 with ONE rounding: truncate to f32 and keep the lost bits as a sticky last bit (round to odd: f32 has 13 bits
+// more than f16, so the nearest-even rounding of the odd-rounded value is the nearest-even rounding of d itself)
+__device__ __forceinline__ _Float16 fx_round_f16(double d) {
+  float f = (float)d;
+  if ((double)f != d) {                          // (finite here: |d| < 2^31)
+    unsigned u = __builtin_bit_cast(unsigned, f);
+    if (__builtin_fabs((double)f) > __builtin_fabs(d)) u -= 1u;   // the f32 rounding went away from zero: one step back
+    f = __builtin_bit_cast(float, u | 1u);
+  }
+  return (_Float16)f;
+}
+
+template <typename OutT, bool ACCUM>
+__global__ __launch_bounds__(256) void k_bwd_fx_to_nchw(const fx_cell* __restrict__ acc, int64_t n_cells, int C, int64_t HW,
+                                                        OutT* __restrict__ dst) {
+  __shared__ double tile[32][33];
+  const unsigned char* cls = reinterpret_cast<const unsigned char*>(acc + n_cells);
+  const int64_t b = blockIdx.z, p0 = (int64_t)blockIdx.x * 32;
+  const int c0 = blockIdx.y * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  for (int r = ty; r < 32; r += 8) {
+    const int64_t p = p0 + r;
+    const int c = c0 + tx;
+    if (c < C && p < HW) {
+      const int64_t i = (b * HW + p) * C + c;
+      const unsigned k = cls[i];
+      double v = (double)(long long)acc[i] * (1.0 / kFxScale);
+      if (k) v = k == 1u ? (double)__builtin_inff() : (k == 2u ? -(double)__builtin_inff() : (double)__builtin_nanf(""));
+      tile[r][tx] = v;
+    }
+  }
+  __syncthreads();
+  for (int r = ty; r < 32; r += 8) {
+    const int c = c0 + r;
+    const int64_t p = p0 + tx;
+    if (c < C && p < HW) {
+      OutT* d = dst + (b * C + c) * HW + p;
+      const double v = tile[tx][r];
+      if constexpr (ACCUM) *d = (OutT)((double)*d + v);
+      else if (v != v || __builtin_fabs(v) == (double)__builtin_inff()) *d = (OutT)(float)v;
+      else *d = fx_round_f16(v);
+    }
+  }
+}
+
 // ================================================================= fused input + offset gradient (f16, AlignConv geometry)
 // deform_conv_backward_input_cuda (models/dcn/src/deform_conv_cuda.cpp:262-374) WITHOUT `columns` in HBM.  The reference
 // (and the first version here) materialises columns = W^T x gradOutput [C*9, N] per chunk (604 MB at P3, batch 8), then
@@ -408,11 +485,13 @@ __global__ __launch_bounds__(256) void k_bwd_nchw_to_nhwc(const T* __restrict__ 
   }
 }
 
+// A: the accumulator's cell type -- float (the default: f32 atomics, sums depend on their order) or fx_cell (deterministic mode)
+template <typename A = float>
 __global__ __launch_bounds__(kBThreads) void k_dcn_bwd_input(const _Float16* __restrict__ x,        // NHWC [S,H,W,C]
                                                          const _Float16* __restrict__ go,       // NHWC [S,H,W,O]
                                                          const _Float16* __restrict__ offset,   // NCHW [S,18,H,W]
                                                          const _Float16* __restrict__ wpk,
-                                                         float* __restrict__ grad_in,           // NHWC [S,H,W,C] f32, accumulated
+                                                         A* __restrict__ grad_in,               // NHWC [S,H,W,C] cells, accumulated
                                                          _Float16* __restrict__ grad_off,       // NCHW [S,18,H,W]
                                                          int S, int C, int H, int W, int O) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -436,6 +515,7 @@ __global__ __launch_bounds__(kBThreads) void k_dcn_bwd_input(const _Float16* __r
   const int oy = ty0 - 3, ox = tx0 - 3;
   const int64_t HW = (int64_t)H * W;
   const int KS = O / 16, CC = C / kBCh;
+  [[maybe_unused]] const int64_t n_cells = (int64_t)S * HW * C;   // (fixed point: the class bytes start behind the cells)
 
   // ---- gradOutput tile -> LDS (positions outside the image: zeros), offset-gradient accumulators, sampling table
   for (int v = tid; v < kBPos * (O / 8); v += kBThreads) {
@@ -524,6 +604,26 @@ __global__ __launch_bounds__(kBThreads) void k_dcn_bwd_input(const _Float16* __r
         const unsigned slot = atomicAdd(&s_cur[pix + (k >> 1) * kIPW + (k & 1)], 1u);
         s_list[slot] = ((unsigned)(t * kBPos + pos) << 16) | (unsigned)__builtin_bit_cast(unsigned short, tp.w[k]);
       }
+  }
+  if constexpr (sizeof(A) == 8) {
+    // the slots of a pixel's list were handed out in the order the LDS atomics arrived, and the gather pass sums in list
+    // order in f32: every list is put into ascending order of its entries (no two alike: a (tap, position) reaches a pixel
+    // through one corner only) -- a wave per pixel, an entry's rank = how many of the list are smaller; the room of the
+    // column-gradient tiles, unused before the first chunk, holds the sorted copy
+    __syncthreads();
+    unsigned* s_tmp = reinterpret_cast<unsigned*>(s_G);
+    for (int pix = wave; pix < kIPix; pix += kBThreads / 64) {
+      const unsigned l0 = s_start[pix], l1 = s_start[pix + 1];
+      for (unsigned i = l0 + lane; i < l1; i += 64) {
+        const unsigned key = s_list[i];
+        unsigned rank = 0;
+        for (unsigned j = l0; j < l1; j++) rank += s_list[j] < key ? 1u : 0u;
+        s_tmp[l0 + rank] = key;
+      }
+    }
+    __syncthreads();
+    const unsigned total = s_start[kIPix];
+    for (unsigned e = tid; e < total; e += kBThreads) s_list[e] = s_tmp[e];
   }
 
   // patch of chunk cc: 288 pixels x 4 vectors of 8 channels; vector v -> pixel v >> 2, group v & 3
@@ -660,9 +760,9 @@ __global__ __launch_bounds__(kBThreads) void k_dcn_bwd_input(const _Float16* __r
           const float wk = (float)tp.w[k];
           if (wk == 0.f) continue;
           const int yy = (int)tp.y + (k >> 1), xx = (int)tp.x + (k & 1);
-          float* gp2 = grad_in + ((int64_t)b * HW + (int64_t)yy * W + xx) * C + cc * kBCh + q * 8;
+          const int64_t cell = ((int64_t)b * HW + (int64_t)yy * W + xx) * C + cc * kBCh + q * 8;
 #pragma unroll
-          for (int j = 0; j < 8; j++) atomicAdd(gp2 + j, wk * G[j]);
+          for (int j = 0; j < 8; j++) bwd_acc_add<A>(grad_in, n_cells, cell + j, wk * G[j]);
         }
       }
     }
@@ -699,6 +799,9 @@ __global__ __launch_bounds__(kBThreads) void k_dcn_bwd_input(const _Float16* __r
 #pragma unroll
         for (int k = 0; k < 4; k++) {
           const float wk = l + k < l1 ? (float)__builtin_bit_cast(_Float16, (unsigned short)(ent[k] & 0xffffu)) : 0.f;
+          if constexpr (sizeof(A) == 8) {        // (a repeated entry must stay out of the sum: 0 x inf is NaN)
+            if (!(l + k < l1)) { g0[k] = f32x4b{0.f, 0.f, 0.f, 0.f}; g1[k] = f32x4b{0.f, 0.f, 0.f, 0.f}; }
+          }
 #pragma unroll
           for (int j = 0; j < 4; j++) { a8[it][j] = __builtin_fmaf(wk, g0[k][j], a8[it][j]); a8[it][4 + j] = __builtin_fmaf(wk, g1[k][j], a8[it][4 + j]); }
         }
@@ -719,7 +822,7 @@ __global__ __launch_bounds__(kBThreads) void k_dcn_bwd_input(const _Float16* __r
       const int pix = i >> 5, c = i & 31;
       if (s_start[pix] == s_start[pix + 1]) continue;            // (pixels outside the image have no list: w = 0 there)
       const int yy = oy + pix / kIPW, xx = ox + pix % kIPW;
-      atomicAdd(grad_in + ((int64_t)b * HW + (int64_t)yy * W + xx) * C + cc * kBCh + c, s_sum[pix * kBGRow + c]);
+      bwd_acc_add<A>(grad_in, n_cells, ((int64_t)b * HW + (int64_t)yy * W + xx) * C + cc * kBCh + c, s_sum[pix * kBGRow + c]);
     }
   }
   __syncthreads();
@@ -2153,6 +2256,9 @@ extern "C" int s2a_deformable_col2im(const void* columns, const void* offset, vo
   const int64_t n = (int64_t)g.C * g.kh * g.kw * g.S * g.Ho * g.Wo;
   if (n == 0) return S2A_OK;
   S2A_CHECK_ARG(columns && offset && grad_im_f32, "deformable_col2im: NULL tensor");
+  // (a scatter of float atomics into the caller's accumulator)
+  S2A_CHECK_ARG(!deterministic(), "deformable_col2im: the unfused input gradient has no deterministic implementation "
+                "(deterministic mode is on: s2a_set_deterministic)");
   hipStream_t st = as_stream(stream);
   if (p->dtype == S2A_DTYPE_F64) {
     k_def_col2im<double><<<grid_for(n), 256, 0, st>>>(n, (const double*)columns, (const double*)offset, g, (double*)grad_im_acc);
@@ -2217,12 +2323,14 @@ struct FusedBwdArgs {
   int64_t B, C, H, W, O;
 };
 
-size_t fused_bwd_workspace(int dtype, bool want_input, bool want_weight, int64_t B, int64_t C, int64_t H, int64_t W, int64_t O) {
+// det: the mode the call is issued in (s2a_get_deterministic()): the f16 input gradient then sums into 8-byte fixed-point cells
+// followed by one class byte per cell, 9 bytes per element instead of the f32 accumulator's 4
+size_t fused_bwd_workspace(int dtype, bool want_input, bool want_weight, int64_t B, int64_t C, int64_t H, int64_t W, int64_t O, bool det) {
   // (sizes and types the entry points refuse have no workspace: 0, as the other queries answer them)
   if ((dtype != S2A_DTYPE_F16 && dtype != S2A_DTYPE_F32) || B < 0 || C <= 0 || H < 3 || W < 3 || O <= 0) return 0;
   const size_t el = dtype == S2A_DTYPE_F16 ? 2 : 4;
   size_t n = align_up((size_t)(B * H * W * C) * el) + align_up((size_t)(B * H * W * O) * el) + 1024;
-  if (want_input) n += align_up((size_t)(O * C * 9) * el) + (dtype == S2A_DTYPE_F16 ? align_up((size_t)(B * H * W * C) * 4) : 0);
+  if (want_input) n += align_up((size_t)(O * C * 9) * el) + (dtype == S2A_DTYPE_F16 ? align_up((size_t)(B * H * W * C) * (det ? 9 : 4)) : 0);
   if (want_weight) n += align_up((size_t)kWgradMaxBlocks * O * 192 * 4);
   return n;
 }
@@ -2232,6 +2340,10 @@ int fused_bwd_run(const FusedBwdArgs& a, void* workspace, size_t workspace_bytes
   constexpr bool kHalf = sizeof(T) == 2;
   const bool want_input = a.grad_input != nullptr, want_weight = a.grad_weight != nullptr;
   const int64_t B = a.B, C = a.C, H = a.H, W = a.W, O = a.O;
+  const bool det = deterministic();              // read once, when the call is issued: a captured graph keeps its mode
+  // (the f32 kernel's atomics add floats straight into the caller's gradInput: there is no accumulator to widen)
+  S2A_CHECK_ARG(kHalf || !want_input || !det, "%s: the float32 input gradient has no deterministic implementation "
+                "(deterministic mode is on: s2a_set_deterministic); use float16 tensors or switch the mode off", who);
   S2A_CHECK_ARG(B >= 0 && C > 0 && H >= 3 && W >= 3 && O > 0, "%s: bad shape", who);
   S2A_CHECK_ARG(H < (1 << 15) && W < (1 << 15), "%s: shape too large", who);
   S2A_CHECK_ARG(O <= 256, "%s: needs out_channels <= 256", who);
@@ -2243,7 +2355,7 @@ int fused_bwd_run(const FusedBwdArgs& a, void* workspace, size_t workspace_bytes
   S2A_CHECK_ARG(a.input && a.offset && a.grad_output, "%s: NULL tensor", who);
   S2A_CHECK_ARG(!want_input || (a.weight && a.grad_offset), "%s: NULL tensor", who);
   // (the workspace is carved into 16-byte vector buffers; a typed f32 gradInput is cleared with 16-byte stores, k_bwd_zero4)
-  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, fused_bwd_workspace(a.dtype, want_input, want_weight, B, C, H, W, O), who);
+  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, fused_bwd_workspace(a.dtype, want_input, want_weight, B, C, H, W, O, det), who);
   S2A_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
   S2A_CHECK_ARG(kHalf || !want_input || !a.grad_input_typed || (reinterpret_cast<uintptr_t>(a.grad_input) & 15) == 0,
                 "%s: a float32 grad_input must be 16-byte aligned", who);
@@ -2253,7 +2365,8 @@ int fused_bwd_run(const FusedBwdArgs& a, void* workspace, size_t workspace_bytes
   T* gn = cv.take<T>((size_t)(B * HW * O));
   T* wp = want_input ? cv.take<T>((size_t)(O * C * 9)) : nullptr;
   // f16: [S,H,W,C] f32 accumulator the tiles' atomics add into (128-byte rows); f32: the caller's gradInput itself
-  float* gacc = (want_input && kHalf) ? cv.take<float>((size_t)(B * HW * C)) : nullptr;
+  // (deterministic mode: 8-byte fixed-point cells and their class bytes in the same place)
+  float* gacc = (want_input && kHalf) ? reinterpret_cast<float*>(cv.take<char>((size_t)(B * HW * C) * (det ? 9 : 4))) : nullptr;
   float* partial = want_weight ? cv.take<float>((size_t)kWgradMaxBlocks * O * 192) : nullptr;
   if (!(xn && gn && (!want_input || (wp && (gacc || !kHalf))) && (!want_weight || partial))) {
     set_error("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, cv.off);
@@ -2263,7 +2376,7 @@ int fused_bwd_run(const FusedBwdArgs& a, void* workspace, size_t workspace_bytes
   // a backward captured into a HIP graph would otherwise sum into a stale accumulator from its second replay on)
   if (want_input && (kHalf || a.grad_input_typed)) {
     float* z = kHalf ? gacc : (float*)a.grad_input;
-    const int64_t nz4 = B * HW * C / 4;          // (C % 32 == 0)
+    const int64_t nz4 = (kHalf && det) ? B * HW * C * 9 / 16 : B * HW * C / 4;          // (C % 32 == 0; cells and class bytes in one fill)
     k_bwd_zero4<<<(unsigned)std::min<int64_t>((nz4 + 255) / 256, 65536), 256, 0, st>>>(reinterpret_cast<f32x4b*>(z), nz4);
   }
   auto to_nhwc = [&](const void* src, int64_t ch, T* dst) {
@@ -2284,9 +2397,15 @@ int fused_bwd_run(const FusedBwdArgs& a, void* workspace, size_t workspace_bytes
       k_pack_weight_bwd<<<(unsigned)((wtotal + 255) / 256), 256, 0, st>>>((const _Float16*)a.weight, (int)O, (int)C, wp);
       const int64_t tiles = B * ((H + kBTH - 1) / kBTH) * ((W + kBTW - 1) / kBTW);
       S2A_CHECK_ARG(tiles < (1ll << 31), "%s: too many tiles", who);
-      S2A_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dcn_bwd_input), hipFuncAttributeMaxDynamicSharedMemorySize, kBwdLds));
-      k_dcn_bwd_input<<<(unsigned)tiles, kBThreads, kBwdLds, st>>>(xn, gn, (const _Float16*)a.offset, wp, gacc, (_Float16*)a.grad_offset,
-                                                            (int)B, (int)C, (int)H, (int)W, (int)O);
+      if (det) {
+        S2A_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dcn_bwd_input<fx_cell>), hipFuncAttributeMaxDynamicSharedMemorySize, kBwdLds));
+        k_dcn_bwd_input<fx_cell><<<(unsigned)tiles, kBThreads, kBwdLds, st>>>(xn, gn, (const _Float16*)a.offset, wp, reinterpret_cast<fx_cell*>(gacc),
+                                                                       (_Float16*)a.grad_offset, (int)B, (int)C, (int)H, (int)W, (int)O);
+      } else {
+        S2A_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dcn_bwd_input<float>), hipFuncAttributeMaxDynamicSharedMemorySize, kBwdLds));
+        k_dcn_bwd_input<float><<<(unsigned)tiles, kBThreads, kBwdLds, st>>>(xn, gn, (const _Float16*)a.offset, wp, gacc, (_Float16*)a.grad_offset,
+                                                                     (int)B, (int)C, (int)H, (int)W, (int)O);
+      }
     } else {
       k_pack_weight_bwd_f32<<<(unsigned)((wtotal + 255) / 256), 256, 0, st>>>((const float*)a.weight, (int)O, (int)C, wp);
       const int64_t tiles = B * ((H + kFTH - 1) / kFTH) * ((W + kFTW - 1) / kFTW);
@@ -2303,7 +2422,11 @@ int fused_bwd_run(const FusedBwdArgs& a, void* workspace, size_t workspace_bytes
     }
     if constexpr (kHalf) {
       const dim3 fg((unsigned)((HW + 31) / 32), (unsigned)((C + 31) / 32), (unsigned)B);
-      if (a.grad_input_typed) k_bwd_acc_to_nchw<T, false><<<fg, 256, 0, st>>>(gacc, (int)C, HW, (T*)a.grad_input);
+      if (det) {
+        const fx_cell* cells = reinterpret_cast<const fx_cell*>(gacc);
+        if (a.grad_input_typed) k_bwd_fx_to_nchw<_Float16, false><<<fg, 256, 0, st>>>(cells, B * HW * C, (int)C, HW, (_Float16*)a.grad_input);
+        else k_bwd_fx_to_nchw<float, true><<<fg, 256, 0, st>>>(cells, B * HW * C, (int)C, HW, (float*)a.grad_input);
+      } else if (a.grad_input_typed) k_bwd_acc_to_nchw<T, false><<<fg, 256, 0, st>>>(gacc, (int)C, HW, (T*)a.grad_input);
       else k_bwd_acc_to_nchw<float, true><<<fg, 256, 0, st>>>(gacc, (int)C, HW, (float*)a.grad_input);
     }
     S2A_LAUNCH_CHECK();
@@ -2366,7 +2489,7 @@ int fused_bwd(const FusedBwdArgs& a, void* workspace, size_t workspace_bytes, s2
 // f16: grad_input_f32 [S,C,H,W] is ACCUMULATED (the caller zeroes it), grad_offset [S,18,H,W] f16 is overwritten
 extern "C" size_t s2a_deform_conv_backward_input_workspace_bytes(int64_t batch, int64_t channels, int64_t height,
                                                                  int64_t width, int64_t out_channels) {
-  return fused_bwd_workspace(S2A_DTYPE_F16, true, false, batch, channels, height, width, out_channels);
+  return fused_bwd_workspace(S2A_DTYPE_F16, true, false, batch, channels, height, width, out_channels, s2a::deterministic());
 }
 extern "C" int s2a_deform_conv_backward_input_f16(const void* input, const void* offset, const void* grad_output,
                                                   const void* weight, float* grad_input_f32, void* grad_offset,
@@ -2382,7 +2505,7 @@ extern "C" int s2a_deform_conv_backward_input_f16(const void* input, const void*
 // f32: grad_input [S,C,H,W] is the caller's gradInput, ACCUMULATED in place; grad_offset [S,18,H,W] f32 is overwritten
 extern "C" size_t s2a_deform_conv_backward_input_f32_workspace_bytes(int64_t batch, int64_t channels, int64_t height,
                                                                      int64_t width, int64_t out_channels) {
-  return fused_bwd_workspace(S2A_DTYPE_F32, true, false, batch, channels, height, width, out_channels);
+  return fused_bwd_workspace(S2A_DTYPE_F32, true, false, batch, channels, height, width, out_channels, s2a::deterministic());
 }
 extern "C" int s2a_deform_conv_backward_input_f32(const float* input, const float* offset, const float* grad_output,
                                                   const float* weight, float* grad_input, float* grad_offset,
@@ -2398,7 +2521,7 @@ extern "C" int s2a_deform_conv_backward_input_f32(const float* input, const floa
 // f16: grad_weight_f32 [O,C,3,3] is ACCUMULATED, unscaled (the caller zeroes it and applies `scale`)
 extern "C" size_t s2a_deform_conv_backward_weight_workspace_bytes(int64_t batch, int64_t channels, int64_t height,
                                                                   int64_t width, int64_t out_channels) {
-  return fused_bwd_workspace(S2A_DTYPE_F16, false, true, batch, channels, height, width, out_channels);
+  return fused_bwd_workspace(S2A_DTYPE_F16, false, true, batch, channels, height, width, out_channels, s2a::deterministic());
 }
 extern "C" int s2a_deform_conv_backward_weight_f16(const void* input, const void* offset, const void* grad_output,
                                                    float* grad_weight_f32, int64_t batch, int64_t channels, int64_t height,
@@ -2413,7 +2536,7 @@ extern "C" int s2a_deform_conv_backward_weight_f16(const void* input, const void
 // f32: grad_weight [O,C,3,3] is the caller's gradWeight, += scale * gradOutput x columns^T in place
 extern "C" size_t s2a_deform_conv_backward_weight_f32_workspace_bytes(int64_t batch, int64_t channels, int64_t height,
                                                                       int64_t width, int64_t out_channels) {
-  return fused_bwd_workspace(S2A_DTYPE_F32, false, true, batch, channels, height, width, out_channels);
+  return fused_bwd_workspace(S2A_DTYPE_F32, false, true, batch, channels, height, width, out_channels, s2a::deterministic());
 }
 extern "C" int s2a_deform_conv_backward_weight_f32(const float* input, const float* offset, const float* grad_output,
                                                    float* grad_weight, float scale, int64_t batch, int64_t channels,
@@ -2431,7 +2554,7 @@ extern "C" int s2a_deform_conv_backward_weight_f32(const float* input, const flo
 // either of the two may be NULL to skip that gradient (grad_offset goes with grad_input).
 extern "C" size_t s2a_deform_conv_backward_workspace_bytes(int dtype, int64_t batch, int64_t channels, int64_t height,
                                                            int64_t width, int64_t out_channels) {
-  return fused_bwd_workspace(dtype, true, true, batch, channels, height, width, out_channels);
+  return fused_bwd_workspace(dtype, true, true, batch, channels, height, width, out_channels, s2a::deterministic());
 }
 extern "C" int s2a_deform_conv_backward(int dtype, const void* input, const void* offset, const void* grad_output,
                                         const void* weight, float* grad_input_f32, void* grad_offset, float* grad_weight_f32,

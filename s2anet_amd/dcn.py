@@ -191,6 +191,14 @@ def _cache_step(step, bytes_per_image):
     return best
 
 
+def _no_deterministic_form(what, why):
+    """deterministic mode (s2anet_amd.deterministic): a route whose input gradient is a sum of float atomics is refused, in
+    front of its first launch -- the caller's gradient buffers stay as they are"""
+    raise RuntimeError(f"{what} has no deterministic implementation ({why}); deterministic mode is on "
+                       "(s2anet_amd.deterministic): use float16 tensors with the AlignConv geometry (3x3, stride 1, pad 1, one "
+                       "group, channels % 32 == 0, out_channels % 16 == 0 and <= 256, maps of 3x3 and more) or switch the mode off")
+
+
 def deform_conv_backward_input_cuda(input, offset, gradOutput, gradInput, gradOffset, weight, columns, kW, kH,
                                     dW, dH, padW, padH, dilationW, dilationH, group, deformable_group,
                                     im2col_step):
@@ -210,6 +218,9 @@ def deform_conv_backward_input_cuda(input, offset, gradOutput, gradInput, gradOf
     align_geom = ((kW, kH, dW, dH, padW, padH, dilationW, dilationH) == (3, 3, 1, 1, 1, 1, 1, 1) and group == 1
                   and deformable_group == 1 and C % 32 == 0 and O % 16 == 0 and O <= 256 and H >= 3 and W >= 3
                   and not os.environ.get("S2A_DCN_BWD_UNFUSED"))
+    if _lib.deterministic() and not (align_geom and x.dtype == torch.float16):
+        _no_deterministic_form("deform_conv_backward_input", "the float32 fused kernel adds into gradInput with float atomics"
+                               if align_geom else "the unfused deformable_col2im scatters with float atomics")
     # f32 + AlignConv geometry: the fused dataflow on the f32 matrix instruction (s2a_deform_conv_backward_input_f32),
     # accumulating straight into the caller's gradInput when it is the f32 NCHW tensor deform_conv.py:88 allocates
     if align_geom and x.dtype == torch.float32:
@@ -341,6 +352,8 @@ def _fused_backward(input, offset, weight, grad_output):
     O = weight.shape[0]
     x = input.contiguous()
     dt = x.dtype
+    if dt != torch.float16 and _lib.deterministic():
+        _no_deterministic_form("the fused deformable-conv backward", "the float32 kernel adds into gradInput with float atomics")
     off, go, w = offset.to(dt).contiguous(), grad_output.to(dt).contiguous(), weight.to(dt).contiguous()
     gin = torch.empty((B, C, H, W), dtype=dt, device=x.device)           # overwritten, in the input's own type
     goff = torch.empty((B, 18, H, W), dtype=dt, device=x.device)

@@ -350,34 +350,81 @@ def train_conv_ok(x, conv, residual=None):
     GPU, stride 1, 3x3 / pad 1 or 1x1 / pad 0, channel counts multiples of 64, f16 or f32 parameters, a residual of the
     output's shape and layout, input and output under 2^31 bytes.  The speed heuristics of own_conv_ok play no part:
     a layer on this route is bit-reproducible whatever its size."""
+    return _train_conv_limits(x, conv, residual, conv.in_channels, conv.out_channels)
+
+
+def _train_conv_limits(x, conv, residual, C, O):
+    """train_conv_ok at the channel counts C -> O the kernels would see (the layer's own, or its padded ones: train_pad_widths)"""
+    return _train_limits(x, conv.weight, conv.bias, conv.kernel_size, conv.stride, conv.padding, conv.dilation, conv.groups,
+                         residual, conv.in_channels, conv.out_channels, C, O)
+
+
+def train_filter_ok(x, weight, bias, stride, padding, dilation, groups):
+    """train_conv_ok for a bare [O,C,k,k] filter (ORConv2d's expansion, which is no module's parameter)"""
+    return weight.dim() == 4 and _train_limits(x, weight, bias, weight.shape[2:], stride, padding, dilation, groups, None,
+                                               weight.shape[1], weight.shape[0], weight.shape[1], weight.shape[0])
+
+
+def _train_limits(x, w, b, kernel_size, stride, padding, dilation, groups, residual, c_in, c_out, C, O):
+    """c_in -> c_out: the layer's own widths (what x and the residual must have); C -> O: the widths the kernels would see"""
     if not (x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 and x.numel() > 0 and
             x.is_contiguous(memory_format=torch.channels_last)):
         return False
-    k, pd = tuple(conv.kernel_size), tuple(conv.padding)
-    if not (tuple(conv.dilation) == (1, 1) and conv.groups == 1 and tuple(conv.stride) == (1, 1) and
+    k, pd = tuple(kernel_size), tuple(padding)
+    if not (tuple(dilation) == (1, 1) and groups == 1 and tuple(stride) == (1, 1) and
             ((k == (3, 3) and pd == (1, 1)) or (k == (1, 1) and pd == (0, 0))) and
-            conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0 and x.shape[1] == conv.in_channels):
+            C % 64 == 0 and O % 64 == 0 and x.shape[1] == c_in):
         return False
-    w, b = conv.weight, conv.bias
     if w.dtype not in (torch.float16, torch.float32) or not w.is_cuda or (b is not None and b.dtype != w.dtype):
         return False
     B, _, H, W = x.shape
     if residual is not None and not (residual.is_cuda and residual.dtype == torch.float16 and
-                                     tuple(residual.shape) == (B, conv.out_channels, H, W) and
+                                     tuple(residual.shape) == (B, c_out, H, W) and
                                      residual.is_contiguous(memory_format=torch.channels_last)):
         return False
-    return x.numel() * 2 < (1 << 31) and B * H * W * conv.out_channels * 2 < (1 << 31)
+    return B * H * W * C * 2 < (1 << 31) and B * H * W * O * 2 < (1 << 31)
+
+
+def train_pad_widths(x, conv):
+    """deterministic mode only: (C', O') when the layer fails train_conv_ok for its width alone and passes at the zero-padded
+    width -- fewer than 64 filters (the 5- and 15-map prediction convs: O' = 64) over C % 64 == 0 or C == 32 inputs, or 32
+    inputs (odm_cls_ls[0] behind the orientation pooling: C' = 64) under O % 64 == 0 filters; None otherwise"""
+    C, O = conv.in_channels, conv.out_channels
+    Cp, Op = (64 if C == 32 else C), (64 if 0 < O < 64 else O)
+    if (Cp, Op) == (C, O) or not _train_conv_limits(x, conv, None, Cp, Op):
+        return None
+    return Cp, Op
+
+
+def padded_train_conv(x, weight, bias, relu, Cp, Op):
+    """FusedConvFunction at the padded width: filter rows and bias (O -> O') and filter columns and input (C -> C') are
+    zero-padded with stock differentiable ops, the result is the [:, :O] view -- autograd slices the gradients back.  The
+    padded products are exact zeros, so every real entry is the sum the kernel forms at the layer's own width."""
+    O, C = weight.shape[:2]
+    if Cp != C:
+        x = F.pad(x, (0, 0, 0, 0, 0, Cp - C)).contiguous(memory_format=torch.channels_last)
+    if (Cp, Op) != (C, O):
+        weight = F.pad(weight, (0, 0, 0, 0, 0, Cp - C, 0, Op - O))
+    if bias is not None and Op != O:
+        bias = F.pad(bias, (0, Op - O))
+    out = FusedConvFunction.apply(x, weight, bias, None, relu)
+    return out if Op == O else out[:, :O]
 
 
 def train_kernels(module, enabled=True):
     """own_grad = enabled on every FusedConv2d of the tree -> how many were set.  With own_grad a grad-enabled forward of
     an eligible layer (train_conv_ok) runs FusedConvFunction: forward, input gradient, weight gradient, bias gradient and
-    ReLU mask on the project's kernels.  Every other layer and every other call keeps its route."""
+    ReLU mask on the project's kernels.  Every other layer and every other call keeps its route.
+    In deterministic mode (s2anet_amd.deterministic) own_grad also takes the layers that fail train_conv_ok for their width
+    alone (train_pad_widths) and, set here as well but not counted, the ORConv2d modules of the tree."""
+    from .orn import ORConv2d
     n = 0
     for m in module.modules():
         if isinstance(m, FusedConv2d):
             m.own_grad = bool(enabled)
             n += 1
+        elif isinstance(m, ORConv2d):
+            m.own_grad = bool(enabled)
     return n
 
 
@@ -500,6 +547,10 @@ class FusedConv2d(nn.Conv2d):
         if out is None and self.own_grad and _needs_grad(x, self.weight, self.bias, residual) and \
                 train_conv_ok(x, self, residual):
             return FusedConvFunction.apply(x, self.weight, self.bias, residual, self.fuse_relu)   # (chain= is ignored, as under grad)
+        if out is None and residual is None and self.own_grad and _lib.deterministic() and _needs_grad(x, self.weight, self.bias):
+            pad = train_pad_widths(x, self)
+            if pad is not None:     # deterministic mode: the library's weight gradient is not reproducible, the padded own route is
+                return padded_train_conv(x, self.weight, self.bias, self.fuse_relu, *pad)
         if out is not None:
             assert x.is_cuda and self.bias is not None and not torch.is_grad_enabled() and not own_conv_ok(
                 x, self.in_channels, self.out_channels, self.kernel_size, self.stride, self.padding, self.dilation, self.groups)

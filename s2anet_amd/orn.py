@@ -228,8 +228,18 @@ class ORConv2d(nn.Conv2d):
             self._packed = c = PackedWeightCache()
         return c
 
+    own_grad = False        # fused.train_kernels(): in deterministic mode a grad-enabled forward runs FusedConvFunction
+
     def forward(self, input):
         w = self.rotate_arf()
+        if self.own_grad and input.is_cuda and _lib.deterministic():
+            from .fused import FusedConvFunction, _needs_grad, train_filter_ok
+            # deterministic mode: the convolution on the expanded filter and its gradients on the own kernels; the bank's
+            # gradient is autograd's step through active_rotating_filter (s2a_arf_backward, f32 sums in a fixed order).
+            # An input outside the kernels' limits (not f16 channels-last, ...) keeps the routes below, as a FusedConv2d does.
+            if _needs_grad(input, self.weight, self.bias) and train_filter_ok(input, w, self.bias, self.stride, self.padding,
+                                                                               self.dilation, self.groups):
+                return FusedConvFunction.apply(input, w, self.bias, None, False)
         if input.is_cuda and not torch.is_grad_enabled():
             from .fused import own_conv_ok, conv_f16
             if own_conv_ok(input, w.shape[1], w.shape[0], w.shape[2:], self.stride, self.padding, self.dilation,
