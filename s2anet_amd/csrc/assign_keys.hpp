@@ -1,4 +1,4 @@
-// Label assignment: the pieces the per-image op (rotated_ops.hip) and the batched op (assign_ops.hip) must share to give
+// Label assignment: the pieces the per-image op and the batched op (both assign_ops.hip) must share to give
 // the same ids -- the order-preserving integer key of an overlap and the anchor validity rule.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -37,6 +37,11 @@ struct Carver {
   }
 };
 
+// side streams + fork / join events of the caller's stream, created on first use (struct: rotated_common.hpp).  The
+// registry is host state that must exist once per process: it lives in rotated_ops.hip; iou_ops.hip forks through it too
+struct SideSet;
+int side_set(hipStream_t caller, SideSet** out);
+
 // greedy NMS scan over a suppression bitmask (rotated_ops.hip), shared with the polygon NMS
 int launch_nms_scan(const unsigned long long* mask, const uint32_t* seg_start, const uint32_t* num_seg,
                     const unsigned long long* mask_off, const uint32_t* nblk, const int32_t* perm_seg,

@@ -1,26 +1,23 @@
-// Rotated-box IoU and rotated (multi-label) NMS for MI355X (gfx950, wave64).
+// Rotated (multi-label, segmented) NMS and the detector's candidate compaction for MI355X (gfx950, wave64).
 // COMPILE WITH -ffp-contract=off (see rbox_geom.hpp).
+// (Box IoU: iou_ops.hip.  Label assignment: assign_ops.hip.  What the three share: rotated_common.hpp.)
 //
-// Replaces the reference's three CUDA extensions:
-//   utils/box_iou_rotated/src/box_iou_rotated_cuda.cu:14-101
+// Replaces the reference's two NMS CUDA extensions:
 //   utils/nms_rotated/src/nms_rotated_cuda.cu:14-133
 //   utils/ml_nms_rotated/src/nms_rotated_cuda.cu:14-137
 //
-// MI355X-first structure (not the reference's one-thread-per-pair tiles):
+// MI355X-first structure (not the reference's one-thread-per-pair tiles); the first three steps are those of the box IoU
+// (iou_ops.hip has the long form), the "NMS" section below has the whole pipeline:
 //   1. per-box pre-pass: double cos/sin once per box (PreBox), not once per pair
-//   2. CULL pass: every pair gets a 10-instruction circumscribed-circle test that is
-//      provably exact (culled => the reference returns exactly 0.0f).  Surviving pairs
-//      (~1 % of random DOTA-like boxes) are compacted — LDS queue per workgroup, one
-//      global atomic per flush — into a dense pair list
-//   3. HEAVY pass: the divergent, register-hungry clipping/hull code runs on the dense
-//      list with all 64 lanes busy; its <=24 candidate points sit in LDS ([point][thread]
-//      float2, conflict-free) instead of scratch
-//   4. NMS only: segments (= label runs, or image*class for the batched detector) are
-//      processed independently on upper-triangle 64x64 tiles; the suppression bitmask
-//      stays in HBM, is scanned ON DEVICE (one workgroup per segment, wave-level
-//      readlane resolve of each diagonal word) and the keep list is compacted on device
-//      in score order.  No device->host mask copy (reference cuda.cu:109), no host scan
-//      (:120-131).
+//   2. CULL pass: an exact circumscribed-circle test per pair; the survivors are compacted -- LDS queue per workgroup, one
+//      global atomic per flush -- into a dense pair list
+//   3. HEAVY pass: the divergent, register-hungry clipping/hull code runs on the dense list with all 64 lanes busy
+//   4. segments (= label runs, or image*class for the batched detector) are processed independently; the greedy order is
+//      resolved ON DEVICE and the keep list is compacted on device in score order.  No device->host mask copy (reference
+//      cuda.cu:109), no host scan (:120-131).
+//
+// Host state that exists once per process is defined here, whoever uses it: the side-stream registry (side_set, which
+// iou_ops.hip reaches through common.hpp), the small path's slot pool and g_small_ctl.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,20 +30,15 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "assign_keys.hpp"
 #include "common.hpp"
 #include "rbox_geom.hpp"
+#include "rotated_common.hpp"
 
 namespace s2a {
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kLdsQueue = 1024;      // entries per workgroup queue; a dense-stage batch adds at most 256
 constexpr int kFlushAt = kLdsQueue - 256;
-constexpr int kPersistentGrid = 1024;
-constexpr int kIouCap = 8;               // candidate-point slots per lane of the fast exact-IoU passes (rbox_iou)
-constexpr uint32_t kIouRedo = 0x7fc5a5a5u;   // marker of a pair that needs all 24 slots
-constexpr int kHeavyGrid = 2048;         // 8 workgroups per CU
 constexpr unsigned kScanCacheWords = 6144;  // 48 KB of suppression mask cached in LDS per segment
 
 __device__ __forceinline__ uint32_t float_sortable(float f) {
@@ -57,22 +49,7 @@ __device__ __forceinline__ float sortable_float(uint32_t u) {
   return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
 
-// ---------------------------------------------------------------- pre-pass
-// both box sets of box_iou_rotated in one launch; the first threads also reset the per-chunk pair counters
-__global__ void k_prep_boxes2(const float* __restrict__ b1, int64_t n, PreBox* __restrict__ o1,
-                              const float* __restrict__ b2, int64_t m, PreBox* __restrict__ o2,
-                              unsigned long long* __restrict__ counters, int ncounters) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < ncounters) counters[i] = 0ull;
-  if (i < n) {
-    const float* b = b1 + 5 * i;
-    o1[i] = make_prebox(b[0], b[1], b[2], b[3], b[4], 0.f);
-  } else if (i < n + m) {
-    const float* b = b2 + 5 * (i - n);
-    o2[i - n] = make_prebox(b[0], b[1], b[2], b[3], b[4], 0.f);
-  }
-}
-
+// pre-pass of ONE box set (the NMS builds its PreBoxes in k_nms_pos_meta and launches this nowhere today)
 __global__ void k_prep_boxes(const float* __restrict__ boxes5, int64_t n, PreBox* __restrict__ out) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -80,180 +57,6 @@ __global__ void k_prep_boxes(const float* __restrict__ boxes5, int64_t n, PreBox
   out[i] = make_prebox(b[0], b[1], b[2], b[3], b[4], 0.f);
 }
 
-// ---------------------------------------------------------------- workgroup pair queue
-struct PairQueue {
-  uint2* q;            // LDS, kLdsQueue entries
-  unsigned* count;     // LDS
-  unsigned* base;      // LDS (flush broadcast)
-};
-
-__device__ __forceinline__ void queue_push(PairQueue& Q, unsigned i, unsigned j) {
-  unsigned p = atomicAdd(Q.count, 1u);
-  Q.q[p] = make_uint2(i, j);
-}
-
-// all threads of the workgroup call this; copies the LDS queue to the global list
-__device__ __forceinline__ void queue_flush(PairQueue& Q, uint2* __restrict__ gq,
-                                            unsigned long long* __restrict__ gcount,
-                                            unsigned long long cap) {
-  __syncthreads();
-  unsigned cnt = *Q.count;
-  if (cnt == 0) return;  // uniform
-  if (threadIdx.x == 0) {
-    unsigned long long b = atomicAdd(gcount, (unsigned long long)cnt);
-    Q.base[0] = (unsigned)(b & 0xffffffffu);
-    Q.base[1] = (unsigned)(b >> 32);
-  }
-  __syncthreads();
-  unsigned long long b = ((unsigned long long)Q.base[1] << 32) | Q.base[0];
-  for (unsigned e = threadIdx.x; e < cnt; e += blockDim.x) {
-    unsigned long long dst = b + e;
-    if (dst < cap) gq[dst] = Q.q[e];  // beyond cap: dropped, gcount keeps the true total
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) *Q.count = 0;
-  __syncthreads();
-}
-
-// ================================================================= box_iou_rotated
-// CULL: workgroup = 1024 columns (4 per lane: one 16-byte store per lane per row) x up to 64 rows.
-// Every element of the tile is stored here as 0.0f -- exact for culled pairs; the ~1 % that survive
-// the cull are also queued and overwritten by the heavy pass (same stream, later kernel).  Row boxes
-// are staged in LDS and read one iteration ahead so no row waits on a load.  HBM-write-bound, so the
-// kernel keeps its LDS small (18 KB: eight workgroups = 32 waves per CU; the first version staged the column
-// boxes as well, 76 KB = two workgroups per CU, and reached a quarter of the write bandwidth).
-// Queue discipline: every decision that all threads must take alike is taken through __syncthreads_or -- a
-// plain read of an LDS counter after a barrier is NOT uniform (a fast wave may already be pushing again).
-constexpr int kIouRowsPerWg = 64;
-constexpr int kIouQueue = 1024;      // LDS pair queue (survivors of BOTH tests); a drain batch adds <= 256
-constexpr int kIouQ1 = 3072;         // first-stage queue: circle-test survivors, (row << 10 | column) per entry
-constexpr int kIouQ1DrainAt = 1024;  // <= 2048 pushes per two rows on top of this
-
-template <bool STORE>
-__global__ __launch_bounds__(kThreads) void k_iou_cull(const PreBox* __restrict__ P1,
-                                                       const PreBox* __restrict__ P2,
-                                                       int64_t row0, int64_t row1, int64_t m,
-                                                       float* __restrict__ out,
-                                                       uint2* __restrict__ gq,
-                                                       unsigned long long* __restrict__ gcount,
-                                                       unsigned long long cap) {
-  __shared__ uint2 s_q[kIouQueue];
-  __shared__ unsigned s_count, s_base[2], s_cnt1;
-  __shared__ PreBox s_rows[kIouRowsPerWg];
-  __shared__ unsigned short s_q1[kIouQ1];
-  PairQueue Q{s_q, &s_count, s_base};
-  if (threadIdx.x == 0) { s_count = 0; s_cnt1 = 0; }
-
-  const int64_t jw = (int64_t)blockIdx.x * kThreads * 4;          // first column of the workgroup
-  const int64_t j0 = jw + threadIdx.x * 4;
-  const int64_t rbeg = row0 + (int64_t)blockIdx.y * kIouRowsPerWg;
-  const int nrows = (int)min((int64_t)kIouRowsPerWg, row1 - rbeg);
-  if (threadIdx.x < nrows) s_rows[threadIdx.x] = P1[rbeg + threadIdx.x];
-  float bx[4], by[4], br[4];
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    PreBox b = {};
-    if (j0 + k < m) b = P2[j0 + k];
-    bx[k] = b.x; by[k] = b.y; br[k] = b.r;
-  }
-  const bool vec_ok = (j0 + 3 < m) && ((m & 3) == 0);   // 16-byte aligned full group
-  __syncthreads();
-
-  // Second stage, dense: every lane takes one circle-test survivor from the LDS queue and runs the
-  // separating-axis test on it (a wave with ANY surviving lane used to run the SAT for all its lanes: 86 % of
-  // the iterations at a 3 % survival rate).  Column boxes come from global memory here (L2-resident, ~3 % of the
-  // pairs).  Called by all threads, after a barrier that made the first-stage pushes visible.
-  auto drain_q1 = [&]() {
-    const unsigned cnt1 = s_cnt1;                          // stable: nobody pushes to s_q1 during a drain
-    for (unsigned e0 = 0; e0 < cnt1; e0 += kThreads) {     // uniform trip count
-      if (__syncthreads_or(s_count > kIouQueue - kThreads)) queue_flush(Q, gq, gcount, cap);
-      const unsigned e = e0 + threadIdx.x;
-      if (e < cnt1) {
-        const unsigned v = s_q1[e], r = v >> 10, jl = v & 1023u;
-        const PreBox B = P2[jw + jl];
-        if (!sat_disjoint(s_rows[r], B)) queue_push(Q, (unsigned)(rbeg + r - row0), (unsigned)(jw + jl));
-      }
-    }
-    __syncthreads();                                       // all entries consumed
-    if (threadIdx.x == 0) s_cnt1 = 0;
-    __syncthreads();
-  };
-
-  PreBox Ai = s_rows[0];
-  for (int r = 0; r < nrows; r++) {
-    const float ax = Ai.x, ay = Ai.y, ar = Ai.r;
-    if (r + 1 < nrows) Ai = s_rows[r + 1];   // next row's box while this one is processed
-    const int64_t i = rbeg + r;
-    (void)i; (void)vec_ok;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      if (j0 + k < m && !surely_disjoint(ax, ay, ar, bx[k], by[k], br[k])) {
-        const unsigned p = atomicAdd(&s_cnt1, 1u);
-        s_q1[p] = (unsigned short)((r << 10) | (threadIdx.x * 4 + k));
-      }
-    }
-    if (STORE) {
-      float* dst = out + i * m + j0;
-      if (vec_ok) {
-        *reinterpret_cast<float4*>(dst) = make_float4(0.f, 0.f, 0.f, 0.f);
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-          if (j0 + k < m) dst[k] = 0.f;
-      }
-    }
-    if ((r & 1) == 1) {          // <= 2048 pushes per two rows: the first-stage queue cannot overflow
-      if (__syncthreads_or(s_cnt1 > kIouQ1DrainAt)) drain_q1();
-    }
-  }
-  __syncthreads();
-  drain_q1();
-  queue_flush(Q, gq, gcount, cap);
-}
-
-// ---- pair finding beside a forked zero-fill (no stores here), with NO LDS traffic in its first stage.  A wave owns 64
-// rows (lane = row) and walks its columns 64 at a time: lane j holds column j's box of the chunk in registers, v_readlane
-// hands column j's circle to all lanes as scalar operands (j is a compile-time constant in the unrolled loop), the
-// verdicts collect in a 64-bit mask per lane.  Second stage without a list: every lane walks its own mask bits and fetches
-// the column box from the owning lane by ds_bpermute (the crossbar, not the banks); the loop runs max-popcount times
-// (5-6 at DOTA-like densities).  Survivors of both tests are staged per wave, one global atomic per workgroup at the end.
-// No barrier in the loop.  Circle test: (ax-bx)^2 + (ay-by)^2 > (1.002 ar + 1e-3 + 1.002 br)^2 -- surely_disjoint's
-// margin with the two factors hoisted into the row and the column; NaNs compare false and are evaluated.
-// (Forms that were built, tested bit-exact, measured and removed again -- DESIGN.md section 4 has the numbers: circle
-// records as LDS broadcast reads with per-wave survivor lists (59 us alone became 79), the same on half the LDS, a dense
-// second stage fed from a list, a grid-binned finder, and one launch per 256 x 256 tile that also fills and evaluates.)
-constexpr int kCrStage = 256;                 // per-wave staged pairs
-__device__ __forceinline__ float lane_bcast(float v, int j) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), j));
-}
-// Hand-off of LDS data between the lanes of ONE wave (no workgroup barrier): the hardware issues a wave's LDS
-// operations in order, so all that is needed is that the COMPILER keeps the order too.  Wavefront-scope fences + the wave
-// barrier emit no instruction; they pin the order of the LDS stores / atomics before against the LDS loads after.
-__device__ __forceinline__ void wave_lds_handoff() {
-#ifdef S2A_ABL_NOFENCE
-  return;
-#endif
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-template <int J0, int J1>
-__device__ __forceinline__ void circle_bits(float ax, float ay, float ar, float cx, float cy, float cr, unsigned& bits) {
-  // two columns per packed-f32 instruction (v_pk_add / v_pk_mul / v_pk_fma_f32; the broadcast column pair is one scalar-pair
-  // operand): 8.5 instead of 12.5 instructions per column.  The test only has to be conservative (a pair with IoU > 0 has
-  // circles that overlap by the 0.2 % margin), so the fused multiply-add is fine here.
-  using f2 = __attribute__((ext_vector_type(2))) float;
-  const f2 ax2 = {ax, ax}, ay2 = {ay, ay}, ar2 = {ar, ar};
-#pragma unroll
-  for (int j = J0; j < J1; j += 2) {
-    const f2 cx2 = {lane_bcast(cx, j), lane_bcast(cx, j + 1)}, cy2 = {lane_bcast(cy, j), lane_bcast(cy, j + 1)};
-    const f2 cr2 = {lane_bcast(cr, j), lane_bcast(cr, j + 1)};
-    const f2 dx = ax2 - cx2, dy = ay2 - cy2, R = ar2 + cr2;
-    const f2 d2 = __builtin_elementwise_fma(dy, dy, dx * dx), R2 = R * R;
-    bits |= (d2[0] > R2[0] ? 0u : 1u) << (j - J0);
-    bits |= (d2[1] > R2[1] ? 0u : 1u) << (j + 1 - J0);
-  }
-}
 // NMS first stage: circle test AND area-ratio test (|la - lc| <= lmax; NaN log-areas never drop a pair), see
 // k_nms_cull_lanes.  The column data ROTATES through the lanes (v_mov_b32_dpp wave_ror:1, one lane per step) instead of
 // being broadcast through v_readlane: the readlane form needs four SGPRs per column -- 128 live ones per half tile, which
@@ -296,173 +99,6 @@ __device__ __forceinline__ void nms_stage1_rot2(float ax, float ay, float ar, fl
     cr[0] = dpp_ror1(cr[0]); cr[1] = dpp_ror1(cr[1]); cl[0] = dpp_ror1(cl[0]); cl[1] = dpp_ror1(cl[1]);
   }
 }
-__global__ __launch_bounds__(kThreads) void k_iou_cull_lanes(const PreBox* __restrict__ P1, const PreBox* __restrict__ P2,
-                                                             int64_t row0, int64_t row1, int64_t m, int cols_per_wg,
-                                                             uint2* __restrict__ gq,
-                                                             unsigned long long* __restrict__ gcount,
-                                                             unsigned long long cap) {
-  __shared__ uint2 s_stage[kThreads / 64][kCrStage];
-  __shared__ unsigned s_left[kThreads / 64];
-  __shared__ unsigned long long s_base;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t wr0 = row0 + ((int64_t)blockIdx.y * (kThreads / 64) + wave) * 64;    // this wave's rows
-  const int64_t row = wr0 + lane;
-  const bool valid = row < row1;
-  PreBox A = {};
-  if (valid) A = P1[row];
-  const float ax = A.x, ay = A.y, ar = A.r * 1.002f + 1e-3f;
-  const int64_t jw = (int64_t)blockIdx.x * cols_per_wg;
-  const int64_t jend = min(m, jw + cols_per_wg);
-  uint2* stage = s_stage[wave];
-  unsigned ns = 0;                               // wave-uniform
-  auto flush = [&]() {
-    unsigned long long base = 0;
-    if (lane == 0) base = atomicAdd(gcount, (unsigned long long)ns);
-    base = ((unsigned long long)(uint32_t)__shfl((int)(base >> 32), 0) << 32) | (uint32_t)__shfl((int)(base & 0xffffffffu), 0);
-    wave_lds_handoff();                          // other lanes' staged pairs
-    for (unsigned k = lane; k < ns; k += 64)
-      if (base + k < cap) gq[base + k] = stage[k];
-    wave_lds_handoff();                          // ... are read before the stage is written again
-    ns = 0;
-  };
-  PreBox Cn = {};                                // next chunk's column box of this lane (one chunk ahead)
-  if (jw + lane < jend) Cn = P2[jw + lane];
-  for (int64_t jc = jw; jc < jend; jc += 64) {
-    const PreBox C = Cn;
-    Cn = PreBox{};
-    if (jc + 64 + lane < jend) Cn = P2[jc + 64 + lane];
-    const int nc = (int)min((int64_t)64, jend - jc);
-    // a column beyond the end gets a circle no row can reach (NaN rows reach everything: masked below)
-    const float cx = C.x, cy = C.y, cr = lane < nc ? C.r * 1.002f : -3.0e38f;
-    unsigned lo = 0, hi = 0;
-    circle_bits<0, 32>(ax, ay, ar, cx, cy, cr, lo);
-    circle_bits<32, 64>(ax, ay, ar, cx, cy, cr, hi);
-    unsigned long long mask = ((unsigned long long)hi << 32) | lo;
-    if (nc < 64) mask &= (1ull << nc) - 1ull;
-    if (!valid) mask = 0;
-    while (__any(mask != 0ull)) {
-      const bool has = mask != 0ull;
-      const int j = has ? __ffsll((long long)mask) - 1 : 0;
-      if (has) mask &= mask - 1ull;
-      PreBox B;
-      B.x = __shfl(C.x, j); B.y = __shfl(C.y, j); B.w = __shfl(C.w, j); B.h = __shfl(C.h, j);
-      B.c2 = __shfl(C.c2, j); B.s2 = __shfl(C.s2, j); B.r = 0.f; B.label = 0.f;
-      const bool hit = has && !sat_disjoint(A, B);
-      const unsigned long long bal = __ballot(hit);
-      if (hit)
-        stage[ns + __popcll(bal & ((1ull << lane) - 1ull))] = make_uint2((unsigned)(row - row0), (unsigned)(jc + j));
-      ns += (unsigned)__popcll(bal);
-      if (ns + 64 > kCrStage) flush();
-    }
-  }
-  if (lane == 0) s_left[wave] = ns;
-  __syncthreads();
-  unsigned before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < kThreads / 64; w++) {
-    if (w < wave) before += s_left[w];
-    all += s_left[w];
-  }
-  if (all == 0) return;                // uniform
-  if (threadIdx.x == 0) s_base = atomicAdd(gcount, (unsigned long long)all);
-  __syncthreads();
-  const unsigned long long base = s_base + before;
-  for (unsigned k = lane; k < ns; k += 64)
-    if (base + k < cap) gq[base + k] = stage[k];
-}
-
-// HEAVY: dense list, one pair per lane, persistent grid.  Values go to a compact buffer (vals[e] for pair e): this pass
-// runs while the zero-fill of the output is still in flight on the side stream, so it must not touch `out`.
-// Two passes: the first gives every lane 8 candidate-point slots (16 KB of LDS per workgroup instead of 48: the exact
-// IoU is a chain of dependent LDS round trips and was latency-bound at 3 waves per SIMD); a pair that produces more than
-// 8 candidates (shared edges, duplicates: never in general position) leaves a marker, and k_iou_scatter redoes the
-// marked pairs with the full 24 slots.  A genuine result with the marker's bits would only be recomputed to itself.
-__global__ __launch_bounds__(kThreads) void k_iou_heavy(const PreBox* __restrict__ P1,
-                                                        const PreBox* __restrict__ P2, int64_t row0,
-                                                        const uint2* __restrict__ gq,
-                                                        const unsigned long long* __restrict__ gcount,
-                                                        unsigned long long cap, float* __restrict__ vals) {
-  __shared__ float2 s_pts[kIouCap * kThreads];
-  const unsigned long long total = *gcount;
-  if (total > cap) return;       // list overflow: k_iou_scatter recomputes the chunk directly
-  for (unsigned long long e = (unsigned long long)blockIdx.x * kThreads + threadIdx.x; e < total;
-       e += (unsigned long long)gridDim.x * kThreads) {
-    uint2 ij = gq[e];
-    PreBox A = P1[row0 + ij.x];
-    PreBox B = P2[ij.y];
-    bool redo = false;
-    const float v = rbox_iou<kThreads, kIouCap>(A, B, s_pts + threadIdx.x, &redo);
-    vals[e] = redo ? __uint_as_float(kIouRedo) : v;
-  }
-}
-
-// after the join with the zero-fill: out[i, j] = vals[e] for the listed pairs.  Overflow fallback: the pair list of this
-// chunk did not fit (extremely dense inputs) -> recompute the whole chunk pair by pair (the divergence that the list
-// avoids is irrelevant when most pairs are heavy anyway).
-__global__ __launch_bounds__(kThreads) void k_iou_scatter(const PreBox* __restrict__ P1, const PreBox* __restrict__ P2,
-                                                          int64_t row0, int64_t row1, int64_t m,
-                                                          float* __restrict__ out, const uint2* __restrict__ gq,
-                                                          const unsigned long long* __restrict__ gcount,
-                                                          unsigned long long cap, const float* __restrict__ vals) {
-  __shared__ float2 s_pts[24 * kThreads];
-  const unsigned long long total = *gcount;
-  if (total > cap) {
-    const int64_t all = (row1 - row0) * m;
-    for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < all; e += (int64_t)gridDim.x * kThreads) {
-      int64_t i = row0 + e / m, j = e % m;
-      PreBox A = P1[i], B = P2[j];
-      if (!surely_disjoint(A.x, A.y, A.r, B.x, B.y, B.r) && !sat_disjoint(A, B))
-        out[i * m + j] = rbox_iou<kThreads>(A, B, s_pts + threadIdx.x);
-    }
-    return;
-  }
-  for (unsigned long long e = (unsigned long long)blockIdx.x * kThreads + threadIdx.x; e < total;
-       e += (unsigned long long)gridDim.x * kThreads) {
-    const uint2 ij = gq[e];
-    float v = vals[e];
-    if (__float_as_uint(v) == kIouRedo)      // more than 8 candidate points in the first pass: all 24 slots here
-      v = rbox_iou<kThreads>(P1[row0 + ij.x], P2[ij.y], s_pts + threadIdx.x);
-    out[(row0 + ij.x) * m + ij.y] = v;
-  }
-}
-
-// small fills by a kernel: hipMemsetAsync nodes of a captured graph were not replayed correctly (ROCm 7.2; see nms_core)
-__global__ void k_fill_u32(uint32_t* __restrict__ p, uint32_t v, size_t count) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < count) p[i] = v;
-}
-inline void fill_u32(void* p, uint32_t v, size_t count, hipStream_t st) {
-  if (count) k_fill_u32<<<(unsigned)((count + 255) / 256), 256, 0, st>>>(static_cast<uint32_t*>(p), v, count);
-}
-
-// 16 bytes per lane, grid-stride: 7 TB/s on MI355X (profiles/r02_nms_200k_pmc_before.txt, k_zero_words)
-// PACE > 0: s_sleep between the stores of a wave -- a fill that runs flat out saturates the memory system and every
-// dependent read of the kernels beside it takes ~10 us (the pair finder stretched from 59 to 110 us whatever it did)
-template <int PACE>
-__global__ __launch_bounds__(256) void k_fill_zero(float* __restrict__ out, unsigned long long n) {
-  const unsigned long long n4 = n / 4, stride = (unsigned long long)gridDim.x * 256;
-  float4* o4 = reinterpret_cast<float4*>(out);
-  for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
-    o4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (PACE > 0) __builtin_amdgcn_s_sleep(PACE);
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) out[n4 * 4 + threadIdx.x] = 0.f;
-}
-
-__global__ __launch_bounds__(kThreads) void k_iou_pairs(const float* __restrict__ b1,
-                                                        const float* __restrict__ b2, int64_t n,
-                                                        float* __restrict__ out) {
-  __shared__ float2 s_pts[24 * kThreads];
-  int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (i >= n) return;
-  const float* a = b1 + 5 * i;
-  const float* b = b2 + 5 * i;
-  PreBox A = make_prebox(a[0], a[1], a[2], a[3], a[4], 0.f);
-  PreBox B = make_prebox(b[0], b[1], b[2], b[3], b[4], 0.f);
-  out[i] = rbox_iou<kThreads>(A, B, s_pts + threadIdx.x);
-}
-
-constexpr unsigned long long kIouQueueCap = 32ull << 20;  // 32 Mi pairs = 256 MiB
 
 // ================================================================= NMS
 // Pipeline of one call (all on the device, no host synchronisation):
@@ -3005,14 +2641,11 @@ finish:
 // zero-fill of a large output beside its pair finding; the NMS prelude runs its three independent sorts side by side.
 // Fork / join is the event pattern that stream capture understands.  Keyed by the caller's stream so that calls on
 // different streams (bench.py keeps three batches in flight) never queue behind each other's side work.
-struct SideSet {
-  int dev = -1;
-  hipStream_t caller = nullptr;
-  hipStream_t s[2] = {nullptr, nullptr};
-  hipEvent_t fork = nullptr, join[2] = {nullptr, nullptr};
-};
+// (struct SideSet: rotated_common.hpp.  side_set has external linkage -- declared in common.hpp -- because the registry
+// must exist once per process and iou_ops.hip forks through it.)
 std::mutex g_side_mutex;
 std::vector<SideSet*> g_sides;
+}  // namespace
 
 int side_set(hipStream_t caller, SideSet** out) {
   int dev = 0;
@@ -3035,6 +2668,7 @@ int side_set(hipStream_t caller, SideSet** out) {
   return S2A_OK;
 }
 
+namespace {
 inline bool stream_capturing(hipStream_t st) {
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   return hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
@@ -3570,16 +3204,10 @@ int nms_dropin(const float* dets, const float* scores, const float* labels, int6
 }  // namespace s2a
 
 namespace s2a {
-int build_flags_rotated() {
-  int f = 0;
-#ifdef S2A_MEASURE
-  f |= 1;
-#endif
-#ifdef S2A_ABL_NOFENCE
-  f |= 2;
-#endif
-  return f;
-}
+// bits 16-23 of s2a_build_flags(): a measurement / ablation build of ANY of the three objects that were one
+int build_flags_iou();
+int build_flags_assign();
+int build_flags_rotated() { return kBuildFlags | build_flags_iou() | build_flags_assign(); }
 // ---- the greedy resolve by rounds over an EDGE list is metric-agnostic too: poly_ops.hip hands over the suppression edges
 // of its polygon IoU (i = the higher-scored row, j = the row it suppresses; positions in descending-score order, ONE segment)
 // and gets the keep flags of the original rows back -- four launched rounds, the per-segment clean-up, the view (the same
@@ -3656,465 +3284,6 @@ int launch_nms_scan(const unsigned long long* mask, const uint32_t* seg_start, c
 }  // namespace s2a
 
 using namespace s2a;
-
-extern "C" size_t s2a_box_iou_rotated_workspace_bytes(int64_t n, int64_t m) {
-  if (n < 0 || m < 0 || n >= (1ll << 31) || m >= (1ll << 31)) return 0;   // (sizes the entry point refuses)
-  if (n == 0 || m == 0) return 256;
-  unsigned long long pairs = (unsigned long long)n * (unsigned long long)m;
-  unsigned long long cap = std::max<unsigned long long>(std::min<unsigned long long>(pairs, kIouQueueCap), (unsigned long long)m * 256);
-  return align_up((size_t)(n + m) * sizeof(PreBox)) * 2 + align_up(cap * (sizeof(uint2) + sizeof(float))) + 8192;
-}
-
-namespace s2a {
-namespace {
-constexpr unsigned long long kIouForkBytes = 8ull << 20;   // smaller outputs: one stream, zero-fill fused into the cull
-}  // namespace
-}  // namespace s2a
-
-extern "C" int s2a_box_iou_rotated(const float* boxes1, int64_t n, const float* boxes2, int64_t m,
-                                   float* ious, void* workspace, size_t workspace_bytes,
-                                   s2a_stream_t stream) {
-  S2A_CHECK_ARG(n >= 0 && m >= 0, "box_iou_rotated: negative size");
-  if (n == 0 || m == 0) return S2A_OK;  // reference: empty [N,M] (cuda.cu:79)
-  S2A_CHECK_ARG(boxes1 && boxes2 && ious, "box_iou_rotated: NULL tensor");
-  S2A_CHECK_ARG(n < (1ll << 31) && m < (1ll << 31), "box_iou_rotated: size out of range");
-  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, s2a_box_iou_rotated_workspace_bytes(n, m), "box_iou_rotated");
-  hipStream_t st = as_stream(stream);
-  Carver cv(workspace, workspace_bytes);
-  PreBox* P1 = cv.take<PreBox>((size_t)n);
-  PreBox* P2 = cv.take<PreBox>((size_t)m);
-  unsigned long long* counters = cv.take<unsigned long long>(512);
-  if (!P1 || !P2 || !counters ||
-      cv.off + (size_t)m * 256 * (sizeof(uint2) + sizeof(float)) + 512 > workspace_bytes) {
-    set_error("box_iou_rotated: workspace too small (%zu bytes)", workspace_bytes);
-    return S2A_EWORKSPACE;
-  }
-  unsigned long long cap = (workspace_bytes - cv.off - 256) / (sizeof(uint2) + sizeof(float));
-  uint2* gq = reinterpret_cast<uint2*>(static_cast<char*>(workspace) + cv.off);
-  float* vals = reinterpret_cast<float*>(static_cast<char*>(workspace) + align_up(cv.off + cap * sizeof(uint2)) );
-  cap = std::min<unsigned long long>(cap, (workspace_bytes - (size_t)(reinterpret_cast<char*>(vals) - static_cast<char*>(workspace))) / sizeof(float));
-  // rows per chunk: sized for up to 1/4 of the pairs surviving the cull (DOTA-like inputs: ~1 %);
-  // a denser chunk overflows the list and is recomputed pair by pair in k_iou_scatter
-  int64_t rows_per_chunk = (int64_t)std::min<unsigned long long>((unsigned long long)n, 4 * (cap / (unsigned long long)m));
-  if (rows_per_chunk < n) rows_per_chunk = std::max<int64_t>(256, rows_per_chunk / 256 * 256);   // (else: one chunk)
-  int64_t chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
-  if (chunks > 512) {
-    set_error("box_iou_rotated: workspace too small for %lld x %lld", (long long)n, (long long)m);
-    return S2A_EWORKSPACE;
-  }
-  // Large outputs are write-bound (4 B per pair, ~1 % of DOTA-like pairs overlap): the zero-fill of the whole matrix
-  // runs on a side stream at the full store rate while this stream finds the overlapping pairs and evaluates them into a
-  // compact buffer; after the join a small kernel drops the values into place.  (Round 1 stored the zeros from the cull
-  // kernel -- 4 TB/s beside its circle tests -- and ran the dense pass after it: 212 us at 10 k x 10 k.)
-  const bool big = (unsigned long long)n * (unsigned long long)m * 4ull >= kIouForkBytes;
-  const char* ef = getenv("S2A_IOU_FORK");                 // A/B: 0 = never fork, 1 = always
-  const bool fork = ef && (ef[0] == '0' || ef[0] == '1') ? ef[0] == '1' : big;
-  SideSet* ss = nullptr;
-  hipStream_t side = nullptr;
-  if (fork) {
-    int rc = side_set(st, &ss);
-    if (rc != S2A_OK) return rc;
-    side = ss->s[0];
-    S2A_HIP(hipEventRecord(ss->fork, st));
-    S2A_HIP(hipStreamWaitEvent(side, ss->fork, 0));
-    // The fill is PACED (s_sleep between the stores of a wave): flat out it finishes 400 MB in 50-100 us but saturates the
-    // memory system, and every dependent read of the kernels beside it then takes ~10 us -- the pair finder stretched
-    // from 59 to 105-125 us whatever its design and whatever the fill's workgroup count (docs/HISTORY.md, round 3).  At 512
-    // workgroups and s_sleep 12 it moves ~3.5 TB/s (113 us at 10 k x 10 k), ends before the chain beside it does (pair
-    // finding 62 + exact pass 60-65 us, both at their stand-alone speed) and the call takes ~157 us instead of ~195.
-    int fill_wgs = 512, pace = 12;
-#ifdef S2A_MEASURE
-    if (const char* fw = getenv("S2A_IOU_FILL_WGS")) fill_wgs = atoi(fw);     // measurement builds only; 0 = no fill (WRONG results)
-    if (const char* fp = getenv("S2A_IOU_FILL_PACE")) pace = atoi(fp);
-#endif
-    const unsigned long long nm = (unsigned long long)n * (unsigned long long)m;
-    if (fill_wgs > 0) {
-      if (pace >= 12) k_fill_zero<12><<<fill_wgs, 256, 0, side>>>(ious, nm);
-      else if (pace >= 8) k_fill_zero<8><<<fill_wgs, 256, 0, side>>>(ious, nm);
-      else if (pace >= 6) k_fill_zero<6><<<fill_wgs, 256, 0, side>>>(ious, nm);
-      else if (pace >= 4) k_fill_zero<4><<<fill_wgs, 256, 0, side>>>(ious, nm);
-      else if (pace >= 2) k_fill_zero<2><<<fill_wgs, 256, 0, side>>>(ious, nm);
-      else k_fill_zero<0><<<fill_wgs, 256, 0, side>>>(ious, nm);
-    }
-    S2A_HIP(hipEventRecord(ss->join[0], side));
-  }
-  k_prep_boxes2<<<(unsigned)((std::max<int64_t>(n + m, 512) + 255) / 256), 256, 0, st>>>(boxes1, n, P1, boxes2, m, P2, counters, 512);
-  const char* ec = getenv("S2A_IOU_CULL_COLS");            // A/B: round 1's column-major cull beside the forked fill
-  const bool cull_cols = ec && ec[0] == '1';
-  for (int64_t c = 0; c < chunks; c++) {
-    int64_t r0 = c * rows_per_chunk, r1 = std::min(n, r0 + rows_per_chunk);
-    dim3 grid_c((unsigned)((m + kThreads * 4 - 1) / (kThreads * 4)), (unsigned)((r1 - r0 + kIouRowsPerWg - 1) / kIouRowsPerWg));
-    if (fork && !cull_cols) {
-      // columns per workgroup: enough workgroups for ~8 per CU, at least 256 columns each
-      const int64_t rwg = (r1 - r0 + kThreads - 1) / kThreads;
-      int64_t cw = 256;
-      while (cw < m && rwg * ((m + cw - 1) / cw) > 4096) cw *= 2;
-      k_iou_cull_lanes<<<dim3((unsigned)((m + cw - 1) / cw), (unsigned)rwg), kThreads, 0, st>>>(P1, P2, r0, r1, m, (int)cw, gq,
-                                                                                            counters + c, cap);
-    }
-    else if (fork)
-      k_iou_cull<false><<<grid_c, kThreads, 0, st>>>(P1, P2, r0, r1, m, ious, gq, counters + c, cap);
-    else
-      k_iou_cull<true><<<grid_c, kThreads, 0, st>>>(P1, P2, r0, r1, m, ious, gq, counters + c, cap);
-    k_iou_heavy<<<kHeavyGrid, kThreads, 0, st>>>(P1, P2, r0, gq, counters + c, cap, vals);
-    if (fork && c == 0) S2A_HIP(hipStreamWaitEvent(st, ss->join[0], 0));
-    k_iou_scatter<<<kPersistentGrid, kThreads, 0, st>>>(P1, P2, r0, r1, m, ious, gq, counters + c, cap, vals);
-  }
-  S2A_LAUNCH_CHECK();
-  return S2A_OK;
-}
-
-// ================================================================= label assignment (training side)
-// assign_labels (models/utils.py:33-147): the real consumer of box_iou_rotated in the reference.  The [M,N]
-// matrix comes from the cull -> pair list -> dense pass pipeline above (a per-anchor loop over the gts was 10x
-// slower: divergence); three streaming passes over it replace the reference's dozen tensor ops and its
-// Python loop over the gts: (1) one wave per anchor row: validity / range filters in place, row max and
-// first arg-max, rules 1 and 2(1); (2) column maxima (tiled, atomicMax on order-preserving keys);
-// (3) one wave per row: the LAST gt whose column maximum the anchor attains (the reference's ascending loop
-// lets later gts overwrite earlier ones, :131-145).
-namespace s2a {
-namespace {
-// iou_key / key_iou / anchor_valid: assign_keys.hpp (shared with the batched form, assign_ops.hip)
-__global__ __launch_bounds__(256) void k_assign_rows(const float* __restrict__ anchors, float* __restrict__ ious,
-                                                     int64_t M, int64_t N, float img_h, float img_w, float pos_thr,
-                                                     float neg_thr, int filt_anchor, int filt_iou,
-                                                     int64_t* __restrict__ assign) {
-  const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (m >= M) return;
-  const bool valid = !filt_anchor || anchor_valid(anchors + 5 * m, img_h, img_w);
-  float* row = ious + m * N;
-  float best = -2.f;
-  int64_t arg = 0;
-  for (int64_t j = lane; j < N; j += 64) {
-    float v = row[j];
-    if (filt_iou && !(v >= 0.f && v <= 1.f)) v = -0.5f;        // :86-93
-    if (!valid) v = -0.5f;                                     // :97-98
-    v += 0.f;                                                  // -0.0 -> +0.0
-    row[j] = v;
-    if (v > best) { best = v; arg = j; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o);
-    const int64_t oa = __shfl_xor(arg, o);
-    if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }   // first index of the maximum
-  }
-  if (lane == 0) {
-    int64_t a = -2;
-    if (best >= 0.f && best < neg_thr) a = -1;                 // :108
-    if (best >= pos_thr) a = arg;                              // :114-115
-    assign[m] = a;
-  }
-}
-
-// grid (ceil(N/64), ceil(M/256)): thread = one column over 256 rows; rows are read 64 columns wide (coalesced)
-__global__ __launch_bounds__(64) void k_assign_colmax(const float* __restrict__ ious, int64_t M, int64_t N,
-                                                      int* __restrict__ gt_key) {
-  const int64_t j = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  if (j >= N) return;
-  const int64_t m0 = (int64_t)blockIdx.y * 256, m1 = min(M, m0 + 256);
-  int k = 0;
-  for (int64_t m = m0; m < m1; m++) k = max(k, iou_key(ious[m * N + j]));
-  if (k > 0) atomicMax(gt_key + j, k);
-}
-
-__global__ __launch_bounds__(64) void k_assign_colarg(const float* __restrict__ ious, int64_t M, int64_t N,
-                                                      const int* __restrict__ gt_key, int* __restrict__ gt_arg) {
-  const int64_t j = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  if (j >= N) return;
-  const int64_t m0 = (int64_t)blockIdx.y * 256, m1 = min(M, m0 + 256);
-  const int k = gt_key[j];
-  for (int64_t m = m0; m < m1; m++)
-    if (iou_key(ious[m * N + j]) == k) { atomicMin(gt_arg + j, (int)m); break; }   // first row of this chunk
-}
-
-__global__ __launch_bounds__(256) void k_assign_cols(const float* __restrict__ ious, int64_t M, int64_t N,
-                                                     float min_pos_thr, const int* __restrict__ gt_key,
-                                                     const int* __restrict__ gt_arg, int64_t* __restrict__ assign) {
-  const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (m >= M) return;
-  const float* row = ious + m * N;
-  int64_t best = -1;
-  for (int64_t j = lane; j < N; j += 64) {
-    const int k = gt_key[j];
-    if (!(key_iou(k) > min_pos_thr)) continue;                 // :126
-    const bool hit = gt_arg ? gt_arg[j] == (int)m : iou_key(row[j]) == k;
-    if (hit) best = j;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o));
-  if (lane == 0 && best >= 0) assign[m] = best;
-}
-
-// ---- LIST form (round 6): no [M,N] matrix.  The matrix form above is eleven launches (the IoU pipeline alone five) and a
-// strided column-maximum pass: 146 us at 32 gts, 211 us at 300 -- slower than the unfused pair at the sizes models/utils.py:33
-// sees.  Here, for N <= kAtMaxN gts and M x N pairs that fit the list:
-//   k_assign_cull   a workgroup owns 16 anchor rows with ALL gts in LDS: circle + separating-axis test of its 16 x N pairs,
-//                   the survivors into an LDS list, ONE global reservation per workgroup, (row, gt) pairs out;
-//   k_assign_exact  exact IoU of the listed pairs, every lane busy and the whole chip balanced (the 64 P7 anchors of a chip
-//                   overlap most gts: owned by one workgroup they took 0.5 ms): value kept in the list; row maximum / first
-//                   arg-max, the count of filtered entries and the column maxima by atomics;
-//   k_assign_rule3  with the final column maxima: the pairs that attain one -> rule 3 (all anchors), or the first such row;
-//   k_assign_rows   rules 1, 2 (and 3) per anchor; k_assign_last when one anchor per gt is taken.
-// Exact zeros never enter the list (a disjoint pair is 0.0 by the reference's own num == 0 return), so the row rules start
-// from "all zero" and only count filtered (negative) entries.  Needs min_pos_iou_thr >= 0 and pos_iou_thr > 0.
-constexpr int kAtRows = 16, kAtMaxN = 1024;
-constexpr unsigned long long kAtMaxPairs = 8ull << 20;       // list capacity = M x N (never overflows), at most this
-struct AtWs {                                                // carved from the workspace, in this order
-  PreBox* gt_pre; int* gt_key; int* gt_arg; unsigned long long* rowbest; int* nbad; int* r3; unsigned long long* count;
-  uint2* pair; float* val;
-};
-__global__ void k_assign_list_init(const float* __restrict__ gt, int N, int64_t M, AtWs w) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < N) {
-    const float* g = gt + 5 * i;
-    w.gt_pre[i] = make_prebox(g[0], g[1], g[2], g[3], g[4], 0.f);
-    w.gt_key[i] = 0;
-    w.gt_arg[i] = 0x7fffffff;
-  }
-  if (i < M) { w.rowbest[i] = 0ull; w.nbad[i] = 0; w.r3[i] = -1; }
-  if (i == 0) *w.count = 0ull;
-}
-
-__global__ __launch_bounds__(256) void k_assign_cull(const float* __restrict__ anchors, int64_t M, int N, float img_h, float img_w,
-                                                     int filt_anchor, AtWs w) {
-  extern __shared__ __attribute__((aligned(16))) char smem_at[];
-  PreBox* s_gt = reinterpret_cast<PreBox*>(smem_at);                                       // [N]
-  uint32_t* s_list = reinterpret_cast<uint32_t*>(smem_at + (size_t)N * sizeof(PreBox));    // [kAtRows * N]
-  __shared__ PreBox s_anc[kAtRows];
-  __shared__ uint8_t s_valid[kAtRows];
-  __shared__ unsigned s_cnt;
-  __shared__ unsigned long long s_base;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int64_t m0 = (int64_t)blockIdx.x * kAtRows;
-  for (int j = tid; j < N; j += 256) s_gt[j] = w.gt_pre[j];
-  if (tid < kAtRows) {
-    const int64_t m = m0 + tid;
-    bool valid = false;
-    PreBox A = {};
-    if (m < M) {
-      const float* a = anchors + 5 * m;
-      valid = !filt_anchor || anchor_valid(a, img_h, img_w);     // invalid anchors: every overlap is -0.5 (:97-98), nothing to list
-      A = make_prebox(a[0], a[1], a[2], a[3], a[4], 0.f);
-    }
-    s_anc[tid] = A;
-    s_valid[tid] = valid ? 1 : 0;
-  }
-  if (tid == 0) s_cnt = 0;
-  __syncthreads();
-  const int total = kAtRows * N;
-  for (int i0 = 0; i0 < total; i0 += 256) {
-    const int idx = i0 + tid;
-    bool hit = false;
-    int r = 0, j = 0;
-    if (idx < total) {
-      r = idx / N; j = idx - r * N;
-      if (s_valid[r]) {
-        const PreBox& A = s_anc[r];
-        const PreBox& B = s_gt[j];
-        hit = !surely_disjoint(A.x, A.y, A.r, B.x, B.y, B.r) && !sat_disjoint(A, B);
-      }
-    }
-    const unsigned long long bal = __ballot(hit);
-    if (bal) {
-      unsigned base = 0;
-      if (lane == 0) base = atomicAdd(&s_cnt, (unsigned)__popcll(bal));
-      base = (unsigned)__shfl((int)base, 0);
-      if (hit) s_list[base + (unsigned)__popcll(bal & ((1ull << lane) - 1ull))] = ((uint32_t)r << 16) | (uint32_t)j;
-    }
-  }
-  __syncthreads();
-  const unsigned cnt = s_cnt;
-  if (cnt == 0) return;                                          // (uniform)
-  if (tid == 0) s_base = atomicAdd(w.count, (unsigned long long)cnt);
-  __syncthreads();
-  const unsigned long long base = s_base;
-  for (unsigned e = tid; e < cnt; e += 256) {
-    const uint32_t rj = s_list[e];
-    w.pair[base + e] = make_uint2((unsigned)(m0 + (rj >> 16)), rj & 0xffffu);
-  }
-}
-
-__global__ __launch_bounds__(256) void k_assign_exact(const float* __restrict__ anchors, int filt_iou, AtWs w) {
-  __shared__ float2 s_pts[24 * 256];
-  const unsigned long long total = *w.count;
-  for (unsigned long long e = (unsigned long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (unsigned long long)gridDim.x * 256) {
-    const uint2 mj = w.pair[e];
-    const float* a = anchors + 5 * (int64_t)mj.x;
-    const PreBox A = make_prebox(a[0], a[1], a[2], a[3], a[4], 0.f);
-    float v = rbox_iou<256>(A, w.gt_pre[mj.y], s_pts + threadIdx.x);
-    if (filt_iou && !(v >= 0.f && v <= 1.f)) v = -0.5f;          // :86-93
-    v += 0.f;                                                    // -0.0 -> +0.0
-    w.val[e] = v;
-    if (v < 0.f) atomicAdd(w.nbad + mj.x, 1);
-    else if (v > 0.f) {
-      const int k = iou_key(v);
-      atomicMax(w.rowbest + mj.x, ((unsigned long long)(uint32_t)k << 32) | (unsigned long long)(0xffffffffu - mj.y));
-      atomicMax(w.gt_key + mj.y, k);
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void k_assign_rule3(float min_pos_thr, int assign_all, AtWs w) {
-  const unsigned long long total = *w.count;
-  for (unsigned long long e = (unsigned long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (unsigned long long)gridDim.x * 256) {
-    const float v = w.val[e];
-    if (!(v > 0.f)) continue;
-    const uint2 mj = w.pair[e];
-    const int kc = w.gt_key[mj.y];
-    if (key_iou(kc) > min_pos_thr && iou_key(v) == kc) {         // :126: this anchor attains the gt's maximum
-      if (assign_all) atomicMax(w.r3 + mj.x, (int)mj.y);
-      else atomicMin(w.gt_arg + mj.y, (int)mj.x);
-    }
-  }
-}
-
-__global__ void k_assign_rows_list(const float* __restrict__ anchors, int64_t M, int N, float img_h, float img_w, float pos_thr,
-                                   float neg_thr, int filt_anchor, int assign_all, AtWs w, int64_t* __restrict__ assign) {
-  const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (m >= M) return;
-  const bool valid = !filt_anchor || anchor_valid(anchors + 5 * m, img_h, img_w);
-  const unsigned long long b = w.rowbest[m];
-  float best = 0.f;                                              // every entry that was not listed is an exact zero
-  int64_t arg = 0;
-  if (!valid || w.nbad[m] == N) best = -0.5f;                    // :97-98 / every overlap filtered
-  else if (b != 0ull) { best = key_iou((int)(b >> 32)); arg = (int64_t)(0xffffffffu - (uint32_t)(b & 0xffffffffull)); }
-  int64_t a = -2;
-  if (best >= 0.f && best < neg_thr) a = -1;                     // :108
-  if (best >= pos_thr) a = arg;                                  // :114-115
-  if (assign_all && w.r3[m] >= 0) a = w.r3[m];                   // :131-145: the last gt whose maximum the anchor attains
-  assign[m] = a;
-}
-
-// one anchor per gt (gt_max_assign_all = False): gt j's anchor is the first row attaining its maximum (gt_arg); the
-// reference's ascending loop lets a later gt overwrite an earlier one on the same anchor
-__global__ __launch_bounds__(1024) void k_assign_last(const int* __restrict__ gt_key, const int* __restrict__ gt_arg, int N,
-                                                      float min_pos_thr, int64_t* __restrict__ assign) {
-  __shared__ int s_m[kAtMaxN];
-  const int j = threadIdx.x;
-  int mine = -1;
-  if (j < N && key_iou(gt_key[j]) > min_pos_thr && gt_arg[j] != 0x7fffffff) mine = gt_arg[j];
-  if (j < kAtMaxN) s_m[j] = mine;
-  __syncthreads();
-  if (mine < 0) return;
-  for (int k = j + 1; k < N; k++)
-    if (s_m[k] == mine) return;
-  assign[mine] = j;
-}
-
-// no gt boxes (:72-80): valid anchors are negatives, the others stay ignored
-__global__ void k_assign_empty(const float* __restrict__ anchors, int64_t M, float img_h, float img_w, int filt_anchor,
-                               int64_t* __restrict__ assign) {
-  const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (m >= M) return;
-  assign[m] = (!filt_anchor || anchor_valid(anchors + 5 * m, img_h, img_w)) ? -1 : -2;
-}
-}  // namespace
-}  // namespace s2a
-
-extern "C" size_t s2a_assign_labels_workspace_bytes(int64_t num_anchors, int64_t num_gts) {
-  if (num_anchors < 0 || num_gts < 0 || num_anchors >= (1ll << 31) || num_gts >= (1ll << 31)) return 0;   // (refused sizes)
-  const int64_t M = std::max<int64_t>(num_anchors, 1), N = std::max<int64_t>(num_gts, 1);
-  const size_t matrix_form = align_up((size_t)M * N * 4) + 2 * align_up((size_t)N * 4) + s2a_box_iou_rotated_workspace_bytes(M, N) + 1024;
-  const size_t list_form = align_up((size_t)N * 32) + 2 * align_up((size_t)N * 4) + align_up((size_t)M * 8) + 2 * align_up((size_t)M * 4) +
-                           256 + align_up((size_t)M * N * 8) + align_up((size_t)M * N * 4) + 1024;
-  return std::max(matrix_form, (unsigned long long)M * (unsigned long long)N <= (8ull << 20) ? list_form : (size_t)0);
-}
-
-extern "C" int s2a_assign_labels(const float* anchors, int64_t num_anchors, const float* gt_boxes, int64_t num_gts,
-                                 float img_h, float img_w, float pos_iou_thr, float neg_iou_thr, float min_pos_iou_thr,
-                                 int gt_max_assign_all, int filter_invalid_anchors, int filter_invalid_ious,
-                                 int64_t* assign_gt_ids, void* workspace, size_t workspace_bytes, s2a_stream_t stream) {
-  S2A_CHECK_ARG(num_anchors >= 0 && num_gts >= 0 && num_anchors < (1ll << 31) && num_gts < (1ll << 31),
-                "assign_labels: sizes out of range");
-  if (num_anchors == 0) return S2A_OK;
-  S2A_CHECK_ARG(anchors && assign_gt_ids && (gt_boxes || num_gts == 0), "assign_labels: NULL tensor");
-  hipStream_t st = as_stream(stream);
-  const int64_t M = num_anchors, N = num_gts;
-  if (N == 0) {
-    k_assign_empty<<<(unsigned)((M + 255) / 256), 256, 0, st>>>(anchors, M, img_h, img_w, filter_invalid_anchors, assign_gt_ids);
-    S2A_LAUNCH_CHECK();
-    return S2A_OK;
-  }
-  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, s2a_assign_labels_workspace_bytes(M, N), "assign_labels");
-  // list form: no IoU matrix, five short launches (see k_assign_cull).  S2A_ASSIGN_LIST=0: the matrix form (A/B, tests)
-  {
-    const char* e = std::getenv("S2A_ASSIGN_LIST");
-    const unsigned long long mn = (unsigned long long)M * (unsigned long long)N;
-    if (N <= kAtMaxN && mn <= kAtMaxPairs && min_pos_iou_thr >= 0.f && pos_iou_thr > 0.f && !(e && e[0] == '0')) {
-      Carver cvt(workspace, workspace_bytes);
-      AtWs w;
-      w.gt_pre = cvt.take<PreBox>((size_t)N);
-      w.gt_key = cvt.take<int>((size_t)N);
-      w.gt_arg = cvt.take<int>((size_t)N);
-      w.rowbest = cvt.take<unsigned long long>((size_t)M);
-      w.nbad = cvt.take<int>((size_t)M);
-      w.r3 = cvt.take<int>((size_t)M);
-      w.count = cvt.take<unsigned long long>(1);
-      w.pair = cvt.take<uint2>((size_t)mn);
-      w.val = cvt.take<float>((size_t)mn);
-      if (!w.val || !w.pair || !w.count || !w.r3 || !w.nbad || !w.rowbest || !w.gt_arg || !w.gt_key || !w.gt_pre) {
-        set_error("assign_labels: workspace too small (%zu < %zu)", workspace_bytes, cvt.off);
-        return S2A_EWORKSPACE;
-      }
-      const size_t lds = (size_t)N * sizeof(PreBox) + (size_t)kAtRows * N * 4;
-      static bool attr_set = false;
-      if (!attr_set) {
-        S2A_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_assign_cull), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(kAtMaxN * sizeof(PreBox) + (size_t)kAtRows * kAtMaxN * 4)));
-        attr_set = true;
-      }
-      const int64_t mx = std::max<int64_t>(M, N);
-      k_assign_list_init<<<(unsigned)((mx + 255) / 256), 256, 0, st>>>(gt_boxes, (int)N, M, w);
-      k_assign_cull<<<(unsigned)((M + kAtRows - 1) / kAtRows), 256, lds, st>>>(anchors, M, (int)N, img_h, img_w, filter_invalid_anchors, w);
-      k_assign_exact<<<1024, 256, 0, st>>>(anchors, filter_invalid_ious, w);
-      k_assign_rule3<<<1024, 256, 0, st>>>(min_pos_iou_thr, gt_max_assign_all, w);
-      k_assign_rows_list<<<(unsigned)((M + 255) / 256), 256, 0, st>>>(anchors, M, (int)N, img_h, img_w, pos_iou_thr, neg_iou_thr,
-                                                                      filter_invalid_anchors, gt_max_assign_all, w, assign_gt_ids);
-      if (!gt_max_assign_all)
-        k_assign_last<<<1, 1024, 0, st>>>(w.gt_key, w.gt_arg, (int)N, min_pos_iou_thr, assign_gt_ids);
-      S2A_LAUNCH_CHECK();
-      return S2A_OK;
-    }
-  }
-  Carver cv(workspace, workspace_bytes);
-  float* ious = cv.take<float>((size_t)M * N);
-  int* gt_key = cv.take<int>((size_t)N);
-  int* gt_arg = cv.take<int>((size_t)N);
-  const size_t iou_ws = s2a_box_iou_rotated_workspace_bytes(M, N);
-  char* iw = cv.take<char>(iou_ws);
-  if (!ious || !gt_key || !gt_arg || !iw) {
-    set_error("assign_labels: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-    return S2A_EWORKSPACE;
-  }
-  int rc = s2a_box_iou_rotated(anchors, M, gt_boxes, N, ious, iw, iou_ws, stream);
-  if (rc != S2A_OK) return rc;
-  fill_u32(gt_key, 0u, (size_t)N, st);
-  const unsigned gr = (unsigned)((M + 3) / 4);
-  k_assign_rows<<<gr, 256, 0, st>>>(anchors, ious, M, N, img_h, img_w, pos_iou_thr, neg_iou_thr, filter_invalid_anchors,
-                                    filter_invalid_ious, assign_gt_ids);
-  dim3 gc((unsigned)((N + 63) / 64), (unsigned)((M + 255) / 256));
-  k_assign_colmax<<<gc, 64, 0, st>>>(ious, M, N, gt_key);
-  if (!gt_max_assign_all) {
-    fill_u32(gt_arg, 0x7f7f7f7fu, (size_t)N, st);
-    k_assign_colarg<<<gc, 64, 0, st>>>(ious, M, N, gt_key, gt_arg);
-  }
-  k_assign_cols<<<gr, 256, 0, st>>>(ious, M, N, min_pos_iou_thr, gt_key, gt_max_assign_all ? nullptr : gt_arg, assign_gt_ids);
-  S2A_LAUNCH_CHECK();
-  return S2A_OK;
-}
-
-extern "C" int s2a_box_iou_rotated_pairs(const float* boxes1, const float* boxes2, int64_t n,
-                                         float* ious, s2a_stream_t stream) {
-  S2A_CHECK_ARG(n >= 0, "box_iou_rotated_pairs: negative size");
-  if (n == 0) return S2A_OK;
-  S2A_CHECK_ARG(boxes1 && boxes2 && ious, "box_iou_rotated_pairs: NULL tensor");
-  k_iou_pairs<<<(unsigned)((n + kThreads - 1) / kThreads), kThreads, 0, as_stream(stream)>>>(boxes1, boxes2, n, ious);
-  S2A_LAUNCH_CHECK();
-  return S2A_OK;
-}
 
 // ---------------------------------------------------------------- multiclass candidates
 // utils/bbox_nms_rotated.py:29-42 for a whole batch, static shapes, no host round trip:
