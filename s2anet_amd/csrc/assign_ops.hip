@@ -100,9 +100,9 @@ bool carve(Carver& cv, int64_t S, int64_t B, int64_t A, int64_t G, int64_t P, Ab
   w.count = cv.take<unsigned long long>(1);
   w.pair = cv.take<uint2>(p);
   w.val = cv.take<float>(p);
-  return w.sets && w.img && w.img_count && w.gt_img && w.gt_pre && w.gt_key && w.gt_arg && w.rowbest && w.nbad && w.r3 && w.count &&
-         w.pair && w.val;
+  return cv.ok();
 }
+constexpr size_t kAbWsSlack = 1024;   // headroom the query has always declared; no sub-buffer lives in it
 
 __global__ __launch_bounds__(256) void k_ab_init(AbSets t, AbWs w, int64_t rows, int64_t cols, int B) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -468,8 +468,19 @@ bool carve(Carver& cv, int64_t M, int64_t N, AtWs& w) {
   w.count = cv.take<unsigned long long>(1);
   w.pair = cv.take<uint2>(mn);
   w.val = cv.take<float>(mn);
-  return w.val && w.pair && w.count && w.r3 && w.nbad && w.rowbest && w.gt_arg && w.gt_key && w.gt_pre;
+  return cv.ok();
 }
+// the matrix form's: the [M,N] IoU matrix, the column maxima / arg-maxima, and s2a_box_iou_rotated's own workspace
+struct AmWs { float* ious; int *gt_key, *gt_arg; char* iou_ws; size_t iou_bytes; };
+bool carve(Carver& cv, int64_t M, int64_t N, AmWs& w) {
+  w.ious = cv.take<float>((size_t)M * N);
+  w.gt_key = cv.take<int>((size_t)N);
+  w.gt_arg = cv.take<int>((size_t)N);
+  w.iou_bytes = s2a_box_iou_rotated_workspace_bytes(M, N);
+  w.iou_ws = cv.take<char>(w.iou_bytes);
+  return cv.ok();
+}
+constexpr size_t kAssignWsSlack = 1024;   // headroom the query has always declared over either form; no sub-buffer lives in it
 __global__ void k_assign_list_init(const float* __restrict__ gt, int N, int64_t M, AtWs w) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < N) {
@@ -629,10 +640,7 @@ extern "C" size_t s2a_assign_labels_batched_workspace_bytes(int64_t num_sets, in
       batch > 65535 || num_sets * batch * num_anchors >= (1ll << 32) || num_sets * target_capacity >= (1ll << 31) ||
       pair_capacity >= (1ll << 40))
     return 0;
-  Carver cv(nullptr, 0);
-  AbWs w;
-  carve(cv, num_sets, batch, num_anchors, target_capacity, pair_capacity, w);
-  return cv.off + 1024;
+  return carved_bytes<AbWs>(num_sets, batch, num_anchors, target_capacity, pair_capacity) + kAbWsSlack;
 }
 
 extern "C" int s2a_assign_labels_batched(const s2a_anchor_set* sets, int num_sets, int64_t batch, int64_t num_anchors,
@@ -662,14 +670,9 @@ extern "C" int s2a_assign_labels_batched(const s2a_anchor_set* sets, int num_set
   const AbSets t = {set_ptr[0], set_ptr[1], set_ptr[2], set_ptr[3], set_stride[0], set_stride[1], set_stride[2], set_stride[3]};
   S2A_CHECK_ARG(min_pos_iou_thr >= 0.f && pos_iou_thr > 0.f,
                 "assign_labels_batched: needs min_pos_iou_thr >= 0 and pos_iou_thr > 0 (unlisted pairs count as exact zeros)");
-  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, s2a_assign_labels_batched_workspace_bytes(S, B, A, G, P), "assign_labels_batched");
-  S2A_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "assign_labels_batched: workspace must be 16-byte aligned");
-  Carver cv(workspace, workspace_bytes);
   AbWs w;
-  if (!carve(cv, S, B, A, G, P, w)) {
-    set_error("assign_labels_batched: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-    return S2A_EWORKSPACE;
-  }
+  if (int rc = carve_workspace(workspace, workspace_bytes, w, kAbWsSlack, "assign_labels_batched", S, B, A, G, P)) return rc;
+  S2A_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "assign_labels_batched: workspace must be 16-byte aligned");
   hipStream_t st = as_stream(stream);
   const int64_t rows = S * B * A, cols = S * G;
   const unsigned long long cap = (unsigned long long)P;
@@ -694,15 +697,9 @@ extern "C" int s2a_assign_labels_batched(const s2a_anchor_set* sets, int num_set
 extern "C" size_t s2a_assign_labels_workspace_bytes(int64_t num_anchors, int64_t num_gts) {
   if (num_anchors < 0 || num_gts < 0 || num_anchors >= (1ll << 31) || num_gts >= (1ll << 31)) return 0;   // (refused sizes)
   const int64_t M = std::max<int64_t>(num_anchors, 1), N = std::max<int64_t>(num_gts, 1);
-  const size_t matrix_form = align_up((size_t)M * N * 4) + 2 * align_up((size_t)N * 4) + s2a_box_iou_rotated_workspace_bytes(M, N) + 1024;
-  size_t list_form = 0;
-  if ((unsigned long long)M * (unsigned long long)N <= kAtMaxPairs) {
-    Carver cv(nullptr, 0);
-    AtWs w;
-    carve(cv, M, N, w);
-    list_form = cv.off + 1024;
-  }
-  return std::max(matrix_form, list_form);
+  const size_t matrix_form = carved_bytes<AmWs>(M, N);
+  const size_t list_form = (unsigned long long)M * (unsigned long long)N <= kAtMaxPairs ? carved_bytes<AtWs>(M, N) : 0;
+  return std::max(matrix_form, list_form) + kAssignWsSlack;
 }
 
 extern "C" int s2a_assign_labels(const float* anchors, int64_t num_anchors, const float* gt_boxes, int64_t num_gts,
@@ -726,12 +723,8 @@ extern "C" int s2a_assign_labels(const float* anchors, int64_t num_anchors, cons
     const char* e = std::getenv("S2A_ASSIGN_LIST");
     const unsigned long long mn = (unsigned long long)M * (unsigned long long)N;
     if (N <= kAtMaxN && mn <= kAtMaxPairs && min_pos_iou_thr >= 0.f && pos_iou_thr > 0.f && !(e && e[0] == '0')) {
-      Carver cvt(workspace, workspace_bytes);
       AtWs w;
-      if (!carve(cvt, M, N, w)) {
-        set_error("assign_labels: workspace too small (%zu < %zu)", workspace_bytes, cvt.off);
-        return S2A_EWORKSPACE;
-      }
+      if (int rc = carve_workspace(workspace, workspace_bytes, w, kAssignWsSlack, "assign_labels", M, N)) return rc;
       const size_t lds = (size_t)N * sizeof(PreBox) + (size_t)kAtRows * N * 4;
       static bool attr_set = false;
       if (!attr_set) {
@@ -752,29 +745,21 @@ extern "C" int s2a_assign_labels(const float* anchors, int64_t num_anchors, cons
       return S2A_OK;
     }
   }
-  Carver cv(workspace, workspace_bytes);
-  float* ious = cv.take<float>((size_t)M * N);
-  int* gt_key = cv.take<int>((size_t)N);
-  int* gt_arg = cv.take<int>((size_t)N);
-  const size_t iou_ws = s2a_box_iou_rotated_workspace_bytes(M, N);
-  char* iw = cv.take<char>(iou_ws);
-  if (!ious || !gt_key || !gt_arg || !iw) {
-    set_error("assign_labels: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-    return S2A_EWORKSPACE;
-  }
-  int rc = s2a_box_iou_rotated(anchors, M, gt_boxes, N, ious, iw, iou_ws, stream);
+  AmWs w;
+  if (int rc = carve_workspace(workspace, workspace_bytes, w, kAssignWsSlack, "assign_labels", M, N)) return rc;
+  int rc = s2a_box_iou_rotated(anchors, M, gt_boxes, N, w.ious, w.iou_ws, w.iou_bytes, stream);
   if (rc != S2A_OK) return rc;
-  fill_u32(gt_key, 0u, (size_t)N, st);
+  fill_u32(w.gt_key, 0u, (size_t)N, st);
   const unsigned gr = (unsigned)((M + 3) / 4);
-  k_assign_rows<<<gr, 256, 0, st>>>(anchors, ious, M, N, img_h, img_w, pos_iou_thr, neg_iou_thr, filter_invalid_anchors,
+  k_assign_rows<<<gr, 256, 0, st>>>(anchors, w.ious, M, N, img_h, img_w, pos_iou_thr, neg_iou_thr, filter_invalid_anchors,
                                     filter_invalid_ious, assign_gt_ids);
   dim3 gc((unsigned)((N + 63) / 64), (unsigned)((M + 255) / 256));
-  k_assign_colmax<<<gc, 64, 0, st>>>(ious, M, N, gt_key);
+  k_assign_colmax<<<gc, 64, 0, st>>>(w.ious, M, N, w.gt_key);
   if (!gt_max_assign_all) {
-    fill_u32(gt_arg, 0x7f7f7f7fu, (size_t)N, st);
-    k_assign_colarg<<<gc, 64, 0, st>>>(ious, M, N, gt_key, gt_arg);
+    fill_u32(w.gt_arg, 0x7f7f7f7fu, (size_t)N, st);
+    k_assign_colarg<<<gc, 64, 0, st>>>(w.ious, M, N, w.gt_key, w.gt_arg);
   }
-  k_assign_cols<<<gr, 256, 0, st>>>(ious, M, N, min_pos_iou_thr, gt_key, gt_max_assign_all ? nullptr : gt_arg, assign_gt_ids);
+  k_assign_cols<<<gr, 256, 0, st>>>(w.ious, M, N, min_pos_iou_thr, w.gt_key, gt_max_assign_all ? nullptr : w.gt_arg, assign_gt_ids);
   S2A_LAUNCH_CHECK();
   return S2A_OK;
 }

@@ -19,16 +19,20 @@ inline hipStream_t as_stream(s2a_stream_t s) { return reinterpret_cast<hipStream
 
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
-// carve a sub-buffer out of a workspace (256-B aligned); returns nullptr when exhausted
+// carve a sub-buffer out of a workspace (256-B aligned); returns nullptr when exhausted, and ok() is false from then on.  An op
+// lists its sub-buffers ONCE, in a carve(Carver&, sizes..., Ws&) that its entry point and its *_workspace_bytes() query both run
 struct Carver {
   char* base;
   size_t size, off;
+  bool failed = false;
   Carver(void* p, size_t n) : base(static_cast<char*>(p)), size(n), off(0) {}
+  bool ok() const { return !failed; }
   template <typename T>
   T* take(size_t count) {
     size_t bytes = align_up(count * sizeof(T));
     if (base == nullptr || off + bytes > size) {
       off += bytes;  // keep counting so callers can report the need
+      failed = true;
       return nullptr;
     }
     T* r = reinterpret_cast<T*>(base + off);
@@ -36,6 +40,23 @@ struct Carver {
     return r;
   }
 };
+// what the op's carve(Carver&, sizes..., Ws&) takes in all: the null-Carver run behind every such query
+template <typename Ws, typename... Sizes>
+size_t carved_bytes(Sizes... sizes) {
+  Carver cv(nullptr, 0);
+  Ws w;
+  carve(cv, sizes..., w);
+  return cv.off;
+}
+// the entry point's run of the same carve, on the caller's buffer: the workspace contract of include/s2anet_hip.h ("Workspaces")
+// for a need of carve + slack (the op's named constant, as in its query); S2A_OK with w filled, or S2A_EWORKSPACE
+template <typename Ws, typename... Sizes>
+int carve_workspace(void* ws, size_t bytes, Ws& w, size_t slack, const char* who, Sizes... sizes) {
+  Carver cv(ws, bytes);
+  if (carve(cv, sizes..., w) && bytes >= cv.off + slack) return S2A_OK;
+  set_error("%s: workspace too small (%zu < %zu bytes)", who, ws ? bytes : (size_t)0, cv.off + slack);
+  return S2A_EWORKSPACE;
+}
 
 // side streams + fork / join events of the caller's stream, created on first use (struct: rotated_common.hpp).  The
 // registry is host state that must exist once per process: it lives in rotated_ops.hip; iou_ops.hip forks through it too

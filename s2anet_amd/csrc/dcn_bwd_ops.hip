@@ -2323,16 +2323,27 @@ struct FusedBwdArgs {
   int64_t B, C, H, W, O;
 };
 
-// det: the mode the call is issued in (s2a_get_deterministic()): the f16 input gradient then sums into 8-byte fixed-point cells
-// followed by one class byte per cell, 9 bytes per element instead of the f32 accumulator's 4
+// The workspace, in carve order: NHWC copies of input and gradOutput; with the input gradient the packed filter and, f16 only,
+// the [S,H,W,C] accumulator the tiles' atomics add into (f32 adds into the caller's gradInput itself); with the weight gradient
+// the blocks' partial sums.  det: the mode the call is issued in (s2a_get_deterministic()): the accumulator then holds 8-byte
+// fixed-point cells followed by one class byte per cell, 9 bytes per element instead of the f32 accumulator's 4
+struct FusedBwdWs { void *xn, *gn, *wp; float *gacc, *partial; };   // (xn, gn, wp: of `dtype`)
+bool carve(Carver& cv, int dtype, bool want_input, bool want_weight, int64_t B, int64_t C, int64_t H, int64_t W, int64_t O, bool det,
+           FusedBwdWs& w) {
+  const bool half = dtype == S2A_DTYPE_F16;
+  const size_t el = half ? 2 : 4;
+  w.xn = cv.take<char>((size_t)(B * H * W * C) * el);
+  w.gn = cv.take<char>((size_t)(B * H * W * O) * el);
+  w.wp = want_input ? cv.take<char>((size_t)(O * C * 9) * el) : nullptr;
+  w.gacc = (want_input && half) ? reinterpret_cast<float*>(cv.take<char>((size_t)(B * H * W * C) * (det ? 9 : 4))) : nullptr;
+  w.partial = want_weight ? cv.take<float>((size_t)kWgradMaxBlocks * O * 192) : nullptr;
+  return cv.ok();
+}
+constexpr size_t kFusedBwdWsSlack = 1024;   // headroom the five queries have always declared; no sub-buffer lives in it
 size_t fused_bwd_workspace(int dtype, bool want_input, bool want_weight, int64_t B, int64_t C, int64_t H, int64_t W, int64_t O, bool det) {
   // (sizes and types the entry points refuse have no workspace: 0, as the other queries answer them)
   if ((dtype != S2A_DTYPE_F16 && dtype != S2A_DTYPE_F32) || B < 0 || C <= 0 || H < 3 || W < 3 || O <= 0) return 0;
-  const size_t el = dtype == S2A_DTYPE_F16 ? 2 : 4;
-  size_t n = align_up((size_t)(B * H * W * C) * el) + align_up((size_t)(B * H * W * O) * el) + 1024;
-  if (want_input) n += align_up((size_t)(O * C * 9) * el) + (dtype == S2A_DTYPE_F16 ? align_up((size_t)(B * H * W * C) * (det ? 9 : 4)) : 0);
-  if (want_weight) n += align_up((size_t)kWgradMaxBlocks * O * 192 * 4);
-  return n;
+  return carved_bytes<FusedBwdWs>(dtype, want_input, want_weight, B, C, H, W, O, det) + kFusedBwdWsSlack;
 }
 
 template <typename T>
@@ -2355,27 +2366,17 @@ int fused_bwd_run(const FusedBwdArgs& a, void* workspace, size_t workspace_bytes
   S2A_CHECK_ARG(a.input && a.offset && a.grad_output, "%s: NULL tensor", who);
   S2A_CHECK_ARG(!want_input || (a.weight && a.grad_offset), "%s: NULL tensor", who);
   // (the workspace is carved into 16-byte vector buffers; a typed f32 gradInput is cleared with 16-byte stores, k_bwd_zero4)
-  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, fused_bwd_workspace(a.dtype, want_input, want_weight, B, C, H, W, O, det), who);
+  FusedBwdWs w;
+  if (int rc = carve_workspace(workspace, workspace_bytes, w, kFusedBwdWsSlack, who, a.dtype, want_input, want_weight, B, C, H, W, O, det)) return rc;
   S2A_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
   S2A_CHECK_ARG(kHalf || !want_input || !a.grad_input_typed || (reinterpret_cast<uintptr_t>(a.grad_input) & 15) == 0,
                 "%s: a float32 grad_input must be 16-byte aligned", who);
-  Carver cv(workspace, workspace_bytes);
   const int64_t HW = H * W;
-  T* xn = cv.take<T>((size_t)(B * HW * C));
-  T* gn = cv.take<T>((size_t)(B * HW * O));
-  T* wp = want_input ? cv.take<T>((size_t)(O * C * 9)) : nullptr;
-  // f16: [S,H,W,C] f32 accumulator the tiles' atomics add into (128-byte rows); f32: the caller's gradInput itself
-  // (deterministic mode: 8-byte fixed-point cells and their class bytes in the same place)
-  float* gacc = (want_input && kHalf) ? reinterpret_cast<float*>(cv.take<char>((size_t)(B * HW * C) * (det ? 9 : 4))) : nullptr;
-  float* partial = want_weight ? cv.take<float>((size_t)kWgradMaxBlocks * O * 192) : nullptr;
-  if (!(xn && gn && (!want_input || (wp && (gacc || !kHalf))) && (!want_weight || partial))) {
-    set_error("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, cv.off);
-    return S2A_EWORKSPACE;
-  }
+  T *xn = static_cast<T*>(w.xn), *gn = static_cast<T*>(w.gn), *wp = static_cast<T*>(w.wp);
   // (an own fill kernel, not hipMemsetAsync: memset nodes of a captured graph are not replayed correctly on ROCm 7.2, DESIGN 5 --
   // a backward captured into a HIP graph would otherwise sum into a stale accumulator from its second replay on)
   if (want_input && (kHalf || a.grad_input_typed)) {
-    float* z = kHalf ? gacc : (float*)a.grad_input;
+    float* z = kHalf ? w.gacc : (float*)a.grad_input;
     const int64_t nz4 = (kHalf && det) ? B * HW * C * 9 / 16 : B * HW * C / 4;          // (C % 32 == 0; cells and class bytes in one fill)
     k_bwd_zero4<<<(unsigned)std::min<int64_t>((nz4 + 255) / 256, 65536), 256, 0, st>>>(reinterpret_cast<f32x4b*>(z), nz4);
   }
@@ -2399,11 +2400,11 @@ int fused_bwd_run(const FusedBwdArgs& a, void* workspace, size_t workspace_bytes
       S2A_CHECK_ARG(tiles < (1ll << 31), "%s: too many tiles", who);
       if (det) {
         S2A_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dcn_bwd_input<fx_cell>), hipFuncAttributeMaxDynamicSharedMemorySize, kBwdLds));
-        k_dcn_bwd_input<fx_cell><<<(unsigned)tiles, kBThreads, kBwdLds, st>>>(xn, gn, (const _Float16*)a.offset, wp, reinterpret_cast<fx_cell*>(gacc),
+        k_dcn_bwd_input<fx_cell><<<(unsigned)tiles, kBThreads, kBwdLds, st>>>(xn, gn, (const _Float16*)a.offset, wp, reinterpret_cast<fx_cell*>(w.gacc),
                                                                        (_Float16*)a.grad_offset, (int)B, (int)C, (int)H, (int)W, (int)O);
       } else {
         S2A_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dcn_bwd_input<float>), hipFuncAttributeMaxDynamicSharedMemorySize, kBwdLds));
-        k_dcn_bwd_input<float><<<(unsigned)tiles, kBThreads, kBwdLds, st>>>(xn, gn, (const _Float16*)a.offset, wp, gacc, (_Float16*)a.grad_offset,
+        k_dcn_bwd_input<float><<<(unsigned)tiles, kBThreads, kBwdLds, st>>>(xn, gn, (const _Float16*)a.offset, wp, w.gacc, (_Float16*)a.grad_offset,
                                                                      (int)B, (int)C, (int)H, (int)W, (int)O);
       }
     } else {
@@ -2423,11 +2424,11 @@ int fused_bwd_run(const FusedBwdArgs& a, void* workspace, size_t workspace_bytes
     if constexpr (kHalf) {
       const dim3 fg((unsigned)((HW + 31) / 32), (unsigned)((C + 31) / 32), (unsigned)B);
       if (det) {
-        const fx_cell* cells = reinterpret_cast<const fx_cell*>(gacc);
+        const fx_cell* cells = reinterpret_cast<const fx_cell*>(w.gacc);
         if (a.grad_input_typed) k_bwd_fx_to_nchw<_Float16, false><<<fg, 256, 0, st>>>(cells, B * HW * C, (int)C, HW, (_Float16*)a.grad_input);
         else k_bwd_fx_to_nchw<float, true><<<fg, 256, 0, st>>>(cells, B * HW * C, (int)C, HW, (float*)a.grad_input);
-      } else if (a.grad_input_typed) k_bwd_acc_to_nchw<T, false><<<fg, 256, 0, st>>>(gacc, (int)C, HW, (T*)a.grad_input);
-      else k_bwd_acc_to_nchw<float, true><<<fg, 256, 0, st>>>(gacc, (int)C, HW, (float*)a.grad_input);
+      } else if (a.grad_input_typed) k_bwd_acc_to_nchw<T, false><<<fg, 256, 0, st>>>(w.gacc, (int)C, HW, (T*)a.grad_input);
+      else k_bwd_acc_to_nchw<float, true><<<fg, 256, 0, st>>>(w.gacc, (int)C, HW, (float*)a.grad_input);
     }
     S2A_LAUNCH_CHECK();
   }
@@ -2450,7 +2451,7 @@ int fused_bwd_run(const FusedBwdArgs& a, void* workspace, size_t workspace_bytes
       const int gop = (dw + ((16 - (dw & 63)) & 63)) * 4;
       const int lds = kWPos * gop + kWPatchPix * 128 + 3 * kWPos * kWColRow + 3 * kWPos * 16;
       S2A_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dcn_bwd_weight), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      k_dcn_bwd_weight<<<(unsigned)(owners * ksplit), 512, lds, st>>>(xn, gn, (const _Float16*)a.offset, partial, (int)B, (int)C, (int)H,
+      k_dcn_bwd_weight<<<(unsigned)(owners * ksplit), 512, lds, st>>>(xn, gn, (const _Float16*)a.offset, w.partial, (int)B, (int)C, (int)H,
                                                                    (int)W, (int)O, ksplit);
     } else {
       const int64_t tiles = B * ((H + kFTH - 1) / kFTH) * ((W + kFTW - 1) / kFTW);
@@ -2462,17 +2463,17 @@ int fused_bwd_run(const FusedBwdArgs& a, void* workspace, size_t workspace_bytes
       if (wsel && wsel[0] == 'm') {
         const int lds = wgrad_f32_lds_bytes();
         S2A_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dcn_bwd_weight_f32), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        k_dcn_bwd_weight_f32<<<(unsigned)((owners * ksplit + 7) / 8 * 8), kFWThreads, lds, st>>>(xn, gn, (const float*)a.offset, partial, (int)B,
+        k_dcn_bwd_weight_f32<<<(unsigned)((owners * ksplit + 7) / 8 * 8), kFWThreads, lds, st>>>(xn, gn, (const float*)a.offset, w.partial, (int)B,
                                                                                                (int)C, (int)H, (int)W, (int)O, ksplit);
       } else {
         const int lds = wgrad_x3_lds_bytes((int)O);
         S2A_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dcn_bwd_weight_x3), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        k_dcn_bwd_weight_x3<<<(unsigned)(owners * ksplit), 512, lds, st>>>(xn, gn, (const float*)a.offset, partial, (int)B, (int)C, (int)H,
+        k_dcn_bwd_weight_x3<<<(unsigned)(owners * ksplit), 512, lds, st>>>(xn, gn, (const float*)a.offset, w.partial, (int)B, (int)C, (int)H,
                                                                          (int)W, (int)O, ksplit);
       }
     }
     const int64_t nout = O * C * 9;
-    k_dcn_bwd_weight_reduce<<<(unsigned)((nout + 255) / 256), 256, 0, st>>>(partial, a.grad_weight, a.scale, (int)O, (int)C, ksplit);
+    k_dcn_bwd_weight_reduce<<<(unsigned)((nout + 255) / 256), 256, 0, st>>>(w.partial, a.grad_weight, a.scale, (int)O, (int)C, ksplit);
     S2A_LAUNCH_CHECK();
   }
   return S2A_OK;

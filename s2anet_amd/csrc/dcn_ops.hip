@@ -1452,7 +1452,7 @@ extern "C" size_t s2a_deform_conv_workspace_bytes(const s2a_dcn_params* p) {
       (p->dtype != S2A_DTYPE_F32 && p->dtype != S2A_DTYPE_F16 && p->dtype != S2A_DTYPE_F64))
     return 0;   // (parameters the entry point refuses)
   size_t es = esize(p->dtype);
-  size_t b = align_up((size_t)p->out_channels * p->channels * p->kH * p->kW * es * 3) + 256;      // packed filter: f16 two layouts, f32 2.5 x
+  size_t b = align_up((size_t)p->out_channels * p->channels * p->kH * p->kW * es * 3) + 256;      // a BOUND for the fast and the generic path, not the image of a carve (packed filter: f16 two layouts, f32 2.5 x)
   if (p->layout == S2A_LAYOUT_NCHW) b += align_up((size_t)p->batch * p->channels * p->height * p->width * es);
   return b;
 }
@@ -1542,7 +1542,7 @@ extern "C" size_t s2a_align_conv_workspace_bytes(const s2a_align_params* p) {
       (p->dtype != S2A_DTYPE_F32 && p->dtype != S2A_DTYPE_F16))
     return 0;   // (parameters the entry point refuses)
   size_t es = esize(p->dtype);
-  size_t b = align_up((size_t)p->out_channels * p->channels * 9 * es * 3) + 256;      // packed filter: f16 two layouts, f32 2.5 x
+  size_t b = align_up((size_t)p->out_channels * p->channels * 9 * es * 3) + 256;      // a BOUND for the fast and the generic path, not the image of a carve (packed filter: f16 two layouts, f32 2.5 x)
   if (p->layout == S2A_LAYOUT_NCHW) b += align_up((size_t)p->batch * p->channels * p->height * p->width * es);
   return b;
 }

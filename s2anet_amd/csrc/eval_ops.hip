@@ -489,6 +489,55 @@ __global__ void k_eval_finish(const ClassAcc* __restrict__ acc, const uint2* __r
 }
 
 size_t eval_sort_scratch(size_t n) { return n * 40 + (8u << 20); }
+struct EvalWs {                                       // carved from the workspace, in this order
+  unsigned long long *key_a, *key_s; int32_t *idx_a, *ord1; uint32_t *ckey_a, *ckey_s; int32_t* order; uint32_t *gkey_a, *gkey_s;
+  int32_t *rank_a, *grp_rank; double* ov_ws; uint2* cum; uint8_t* flag;                      // [D] each
+  uint2* tile_tot;                                                                           // [D / kEvalScanTile, rounded up]
+  uint32_t *gtkey_a, *gtkey_s; int32_t *gtidx_a, *gt_order, *claim;                          // [G] each
+  uint32_t *gt_off, *seg_start; ClassAcc* acc;                                               // [groups + 1], [kEvalMaxClasses + 2], [kEvalMaxClasses]
+  void* rp; size_t rpb;                                                                      // rocPRIM sort scratch, its bytes
+};
+bool carve(Carver& cv, size_t D, size_t G, size_t groups, EvalWs& w) {
+  w.key_a = cv.take<unsigned long long>(D);
+  w.key_s = cv.take<unsigned long long>(D);
+  w.idx_a = cv.take<int32_t>(D);
+  w.ord1 = cv.take<int32_t>(D);
+  w.ckey_a = cv.take<uint32_t>(D);
+  w.ckey_s = cv.take<uint32_t>(D);
+  w.order = cv.take<int32_t>(D);
+  w.gkey_a = cv.take<uint32_t>(D);
+  w.gkey_s = cv.take<uint32_t>(D);
+  w.rank_a = cv.take<int32_t>(D);
+  w.grp_rank = cv.take<int32_t>(D);
+  w.ov_ws = cv.take<double>(D);
+  w.cum = cv.take<uint2>(D);
+  w.flag = cv.take<uint8_t>(D);
+  w.tile_tot = cv.take<uint2>((D + kEvalScanTile - 1) / kEvalScanTile);
+  w.gtkey_a = cv.take<uint32_t>(G);
+  w.gtkey_s = cv.take<uint32_t>(G);
+  w.gtidx_a = cv.take<int32_t>(G);
+  w.gt_order = cv.take<int32_t>(G);
+  w.claim = cv.take<int32_t>(G);
+  w.gt_off = cv.take<uint32_t>(groups + 1);
+  w.seg_start = cv.take<uint32_t>(kEvalMaxClasses + 2);
+  w.acc = cv.take<ClassAcc>(kEvalMaxClasses);
+  w.rpb = eval_sort_scratch(std::max(D, G));
+  w.rp = cv.take<char>(w.rpb);
+  return cv.ok();
+}
+constexpr size_t kEvalWsSlack = 4096;   // headroom the query has always declared; no sub-buffer lives in it
+// keys / vals [n] sorted by bits [0, bits) of the key into keys_out / vals_out, on the carved scratch
+template <typename K>
+int eval_sort(const EvalWs& w, K* keys, K* keys_out, int32_t* vals, int32_t* vals_out, size_t n, int bits, hipStream_t st) {
+  size_t need = 0;
+  S2A_HIP(rocprim::radix_sort_pairs(nullptr, need, keys, keys_out, vals, vals_out, n, 0, bits, st));
+  if (need > w.rpb) {
+    set_error("eval_task1: workspace too small (sort scratch %zu < %zu bytes)", w.rpb, need);
+    return S2A_EWORKSPACE;
+  }
+  S2A_HIP(rocprim::radix_sort_pairs(w.rp, need, keys, keys_out, vals, vals_out, n, 0, bits, st));
+  return S2A_OK;
+}
 
 int bits_for(uint64_t max_value) {
   int b = 1;
@@ -505,10 +554,7 @@ extern "C" size_t s2a_eval_task1_workspace_bytes(int64_t num_dets, int64_t num_g
   if (num_dets < 0 || num_gts < 0 || num_dets >= (1ll << 31) || num_gts >= (1ll << 31) || num_classes < 1 ||
       num_classes > kEvalMaxClasses || num_images < 1 || ((int64_t)num_classes + 1) * num_images >= (1ll << 31))
     return 0;   // (sizes the entry point refuses)
-  const size_t D = (size_t)num_dets, G = (size_t)num_gts, groups = (size_t)num_classes * (size_t)num_images;
-  const size_t nb = (D + kEvalScanTile - 1) / kEvalScanTile;
-  return align_up(D * 8) * 2 + align_up(D * 4) * 9 + align_up(D * 8) * 2 + align_up(D) + align_up(nb * 8) + align_up(G * 4) * 5 +
-         align_up((groups + 1) * 4) + align_up((kEvalMaxClasses + 2) * 4) + align_up(kEvalMaxClasses * sizeof(ClassAcc)) + align_up(eval_sort_scratch(std::max(D, G))) + 4096;
+  return carved_bytes<EvalWs>((size_t)num_dets, (size_t)num_gts, (size_t)num_classes * (size_t)num_images) + kEvalWsSlack;
 }
 
 extern "C" int s2a_eval_task1(const double* det_polys, const double* det_scores, const int32_t* det_labels,
@@ -532,76 +578,25 @@ extern "C" int s2a_eval_task1(const double* det_polys, const double* det_scores,
   const size_t szD = (size_t)D, szG = (size_t)G, groups = (size_t)C * (size_t)I;
   const size_t nb = (szD + kEvalScanTile - 1) / kEvalScanTile;
   hipStream_t st = as_stream(stream);
-  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, s2a_eval_task1_workspace_bytes(D, G, C, I), "eval_task1");
-  Carver cv(workspace, workspace_bytes);
-  auto* key_a = cv.take<unsigned long long>(szD);
-  auto* key_s = cv.take<unsigned long long>(szD);
-  auto* idx_a = cv.take<int32_t>(szD);
-  auto* ord1 = cv.take<int32_t>(szD);
-  auto* ckey_a = cv.take<uint32_t>(szD);
-  auto* ckey_s = cv.take<uint32_t>(szD);
-  auto* order = cv.take<int32_t>(szD);
-  auto* gkey_a = cv.take<uint32_t>(szD);
-  auto* gkey_s = cv.take<uint32_t>(szD);
-  auto* rank_a = cv.take<int32_t>(szD);
-  auto* grp_rank = cv.take<int32_t>(szD);
-  auto* ov_ws = cv.take<double>(szD);
-  auto* cum = cv.take<uint2>(szD);
-  auto* flag = cv.take<uint8_t>(szD);
-  auto* tile_tot = cv.take<uint2>(nb);
-  auto* gtkey_a = cv.take<uint32_t>(szG);
-  auto* gtkey_s = cv.take<uint32_t>(szG);
-  auto* gtidx_a = cv.take<int32_t>(szG);
-  auto* gt_order = cv.take<int32_t>(szG);
-  auto* claim = cv.take<int32_t>(szG);
-  auto* gt_off = cv.take<uint32_t>(groups + 1);
-  auto* seg_start = cv.take<uint32_t>(kEvalMaxClasses + 2);
-  auto* acc = cv.take<ClassAcc>(kEvalMaxClasses);
-  const size_t rpb = eval_sort_scratch(std::max(szD, szG));
-  void* rp = cv.take<char>(rpb);
-  int32_t* slot_ws = idx_a;                                          // (idx_a is free once the first sort has run)
-  if (!key_a || !key_s || !idx_a || !ord1 || !ckey_a || !ckey_s || !order || !gkey_a || !gkey_s || !rank_a || !grp_rank || !ov_ws ||
-      !cum || !flag || !tile_tot || !gtkey_a || !gtkey_s || !gtidx_a || !gt_order || !claim || !gt_off || !seg_start || !acc || !rp) {
-    set_error("eval_task1: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-    return S2A_EWORKSPACE;
-  }
+  EvalWs w;
+  if (int rc = carve_workspace(workspace, workspace_bytes, w, kEvalWsSlack, "eval_task1", szD, szG, groups)) return rc;
+  int32_t* slot_ws = w.idx_a;                                        // (idx_a is free once the first sort has run)
   const int cbits = bits_for((uint64_t)C), gbits = bits_for((uint64_t)groups);
-  size_t need = 0;
   if (D > 0) {
     const unsigned gd = (unsigned)((D + 255) / 256);
-    k_eval_det_keys<<<gd, 256, 0, st>>>(det_scores, det_labels, det_image, D, C, I, key_a, idx_a);
-    S2A_HIP(rocprim::radix_sort_pairs(nullptr, need, key_a, key_s, idx_a, ord1, szD, 0, 64, st));
-    if (need > rpb) {
-      set_error("eval_task1: workspace too small (sort scratch %zu < %zu bytes)", rpb, need);
-      return S2A_EWORKSPACE;
-    }
-    S2A_HIP(rocprim::radix_sort_pairs(rp, need, key_a, key_s, idx_a, ord1, szD, 0, 64, st));
-    k_eval_class_keys<<<gd, 256, 0, st>>>(ord1, det_labels, det_image, D, C, I, ckey_a);
-    S2A_HIP(rocprim::radix_sort_pairs(nullptr, need, ckey_a, ckey_s, ord1, order, szD, 0, cbits, st));
-    if (need > rpb) {
-      set_error("eval_task1: workspace too small (sort scratch %zu < %zu bytes)", rpb, need);
-      return S2A_EWORKSPACE;
-    }
-    S2A_HIP(rocprim::radix_sort_pairs(rp, need, ckey_a, ckey_s, ord1, order, szD, 0, cbits, st));
-    k_eval_group_keys<<<gd, 256, 0, st>>>(ckey_s, order, det_image, D, C, I, gkey_a, rank_a);
-    S2A_HIP(rocprim::radix_sort_pairs(nullptr, need, gkey_a, gkey_s, rank_a, grp_rank, szD, 0, gbits, st));
-    if (need > rpb) {
-      set_error("eval_task1: workspace too small (sort scratch %zu < %zu bytes)", rpb, need);
-      return S2A_EWORKSPACE;
-    }
-    S2A_HIP(rocprim::radix_sort_pairs(rp, need, gkey_a, gkey_s, rank_a, grp_rank, szD, 0, gbits, st));
+    k_eval_det_keys<<<gd, 256, 0, st>>>(det_scores, det_labels, det_image, D, C, I, w.key_a, w.idx_a);
+    if (int rc = eval_sort(w, w.key_a, w.key_s, w.idx_a, w.ord1, szD, 64, st)) return rc;
+    k_eval_class_keys<<<gd, 256, 0, st>>>(w.ord1, det_labels, det_image, D, C, I, w.ckey_a);
+    if (int rc = eval_sort(w, w.ckey_a, w.ckey_s, w.ord1, w.order, szD, cbits, st)) return rc;
+    k_eval_group_keys<<<gd, 256, 0, st>>>(w.ckey_s, w.order, det_image, D, C, I, w.gkey_a, w.rank_a);
+    if (int rc = eval_sort(w, w.gkey_a, w.gkey_s, w.rank_a, w.grp_rank, szD, gbits, st)) return rc;
   }
   if (G > 0) {
-    k_eval_gt_keys<<<(unsigned)((G + 255) / 256), 256, 0, st>>>(gt_labels, gt_image, G, C, I, gtkey_a, gtidx_a);
-    S2A_HIP(rocprim::radix_sort_pairs(nullptr, need, gtkey_a, gtkey_s, gtidx_a, gt_order, szG, 0, gbits, st));
-    if (need > rpb) {
-      set_error("eval_task1: workspace too small (sort scratch %zu < %zu bytes)", rpb, need);
-      return S2A_EWORKSPACE;
-    }
-    S2A_HIP(rocprim::radix_sort_pairs(rp, need, gtkey_a, gtkey_s, gtidx_a, gt_order, szG, 0, gbits, st));
+    k_eval_gt_keys<<<(unsigned)((G + 255) / 256), 256, 0, st>>>(gt_labels, gt_image, G, C, I, w.gtkey_a, w.gtidx_a);
+    if (int rc = eval_sort(w, w.gtkey_a, w.gtkey_s, w.gtidx_a, w.gt_order, szG, gbits, st)) return rc;
   }
   const int64_t table_n = std::max<int64_t>((int64_t)groups + 1, G);
-  k_eval_tables<<<(unsigned)((table_n + 255) / 256), 256, 0, st>>>(gtkey_s, G, ckey_s, D, C, I, gt_off, seg_start, claim);
+  k_eval_tables<<<(unsigned)((table_n + 255) / 256), 256, 0, st>>>(w.gtkey_s, G, w.ckey_s, D, C, I, w.gt_off, w.seg_start, w.claim);
   EvalOut out = {};
   out.ap = ap; out.precision = precision; out.recall = recall; out.f1 = f1; out.conf = conf;
   out.num_det_at_f1 = reinterpret_cast<long long*>(num_det_at_f1);
@@ -620,18 +615,18 @@ extern "C" int s2a_eval_task1(const double* det_polys, const double* det_scores,
   }
   if (D > 0) {
     k_eval_match<<<(unsigned)((D + kPolyThreads - 1) / kPolyThreads), kPolyThreads, 0, st>>>(
-        gkey_s, grp_rank, order, D, det_polys, gt_polys, gt_order, gt_difficult, gt_off, (uint32_t)groups, ovthresh,
-        is_filter_difficult, ov_ws, slot_ws, claim);
-    k_eval_mark<<<(unsigned)nb, 256, 0, st>>>(ov_ws, slot_ws, claim, gt_order, gt_difficult, seg_start, C, D, ovthresh,
-                                               is_filter_difficult, flag, tile_tot);
-    k_eval_tile_scan<<<1, 1024, 0, st>>>(tile_tot, (int64_t)nb);
-    k_eval_cum<<<(unsigned)nb, 1024, 0, st>>>(flag, tile_tot, D, cum);
+        w.gkey_s, w.grp_rank, w.order, D, det_polys, gt_polys, w.gt_order, gt_difficult, w.gt_off, (uint32_t)groups, ovthresh,
+        is_filter_difficult, w.ov_ws, slot_ws, w.claim);
+    k_eval_mark<<<(unsigned)nb, 256, 0, st>>>(w.ov_ws, slot_ws, w.claim, w.gt_order, gt_difficult, w.seg_start, C, D, ovthresh,
+                                               is_filter_difficult, w.flag, w.tile_tot);
+    k_eval_tile_scan<<<1, 1024, 0, st>>>(w.tile_tot, (int64_t)nb);
+    k_eval_cum<<<(unsigned)nb, 1024, 0, st>>>(w.flag, w.tile_tot, D, w.cum);
   }
   EvalT11 t11;
   for (int k = 0; k < 11; k++) t11.t[k] = thresholds11 ? thresholds11[k] : 0.1 * k;
-  k_eval_class<<<(unsigned)C, 1024, 0, st>>>(cum, seg_start, gt_off, gt_order, gt_difficult, I, is_filter_difficult, t11, acc);
+  k_eval_class<<<(unsigned)C, 1024, 0, st>>>(w.cum, w.seg_start, w.gt_off, w.gt_order, gt_difficult, I, is_filter_difficult, t11, w.acc);
   const int64_t fn = std::max<int64_t>(want_curves ? D : 0, (int64_t)C + 1);
-  k_eval_finish<<<(unsigned)((fn + 255) / 256), 256, 0, st>>>(acc, cum, order, det_scores, ov_ws, slot_ws, gt_order, seg_start, C, D,
+  k_eval_finish<<<(unsigned)((fn + 255) / 256), 256, 0, st>>>(w.acc, w.cum, w.order, det_scores, w.ov_ws, slot_ws, w.gt_order, w.seg_start, C, D,
                                                               use_07_metric, want_curves ? 1 : 0, out);
   S2A_LAUNCH_CHECK();
   return S2A_OK;

@@ -344,6 +344,7 @@ int build_flags_iou() { return kBuildFlags; }   // ORed into build_flags_rotated
 
 using namespace s2a;
 
+// (a declared upper BOUND, not the image of a carve: the call splits whatever follows its three buffers over the two pair lists)
 extern "C" size_t s2a_box_iou_rotated_workspace_bytes(int64_t n, int64_t m) {
   if (n < 0 || m < 0 || n >= (1ll << 31) || m >= (1ll << 31)) return 0;   // (sizes the entry point refuses)
   if (n == 0 || m == 0) return 256;

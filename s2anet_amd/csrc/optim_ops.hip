@@ -284,13 +284,21 @@ __global__ __launch_bounds__(kThreads) void k_optim_apply(const s2a_optim_tensor
   }
 }
 
+struct UpdateWs { Ctrl* ctrl; float* partial; uint32_t* flags; };   // carved from the workspace, in this order
+bool carve(Carver& cv, int64_t n_trained_chunks, UpdateWs& w) {
+  w.ctrl = cv.take<Ctrl>(1);
+  w.partial = cv.take<float>((size_t)n_trained_chunks);
+  w.flags = cv.take<uint32_t>((size_t)n_trained_chunks);
+  return cv.ok();
+}
+constexpr size_t kUpdateWsSlack = 0;   // none: the query is exactly the carve
+
 }  // namespace
 }  // namespace s2a
 
 extern "C" size_t s2a_train_update_workspace_bytes(int64_t n_trained_chunks) {
   if (n_trained_chunks < 0) return 0;
-  const size_t n = (size_t)n_trained_chunks;
-  return s2a::align_up(sizeof(s2a::Ctrl)) + s2a::align_up(n * sizeof(float)) + s2a::align_up(n * sizeof(uint32_t));
+  return s2a::carved_bytes<s2a::UpdateWs>(n_trained_chunks) + s2a::kUpdateWsSlack;
 }
 
 extern "C" int s2a_train_update(const s2a_train_update_args* args, void* workspace, size_t workspace_bytes,
@@ -311,28 +319,21 @@ extern "C" int s2a_train_update(const s2a_train_update_args* args, void* workspa
                 "s2a_train_update: skip flag must be int32 or int64 (skip_elem_bytes 4 or 8, got %d)", a.skip_elem_bytes);
   S2A_CHECK_ARG(!a.scaling_enabled || a.growth_interval > 0, "s2a_train_update: growth_interval must be positive");
   S2A_CHECK_ARG(a.ema_tau > 0.0, "s2a_train_update: ema_tau must be positive");
-  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, s2a_train_update_workspace_bytes(a.n_trained_chunks), "s2a_train_update");
+  UpdateWs w;
+  if (int rc = carve_workspace(workspace, workspace_bytes, w, kUpdateWsSlack, "s2a_train_update", a.n_trained_chunks)) return rc;
   S2A_CHECK_ARG(((uintptr_t)workspace & 15u) == 0, "s2a_train_update: workspace must be 16-byte aligned");
-  Carver ws(workspace, workspace_bytes);
-  Ctrl* ctrl = ws.take<Ctrl>(1);
-  float* partial = ws.take<float>((size_t)a.n_trained_chunks);
-  uint32_t* flags = ws.take<uint32_t>((size_t)a.n_trained_chunks);
-  if (!ctrl || !partial || !flags) {   // (the query and the carving above disagree: never launch on a NULL sub-buffer)
-    set_error("s2a_train_update: workspace too small (%zu < %zu bytes)", workspace_bytes, ws.off);
-    return S2A_EWORKSPACE;
-  }
   hipStream_t st = as_stream(stream);
 
   const bool need_norm = (a.max_norm > 0.0f || a.scaling_enabled) && a.n_trained_chunks > 0;
   if (need_norm) {
     const int grid = (int)(a.n_trained_chunks < kMaxGrid ? a.n_trained_chunks : kMaxGrid);
     k_optim_partials<<<grid, kThreads, 0, st>>>(a.tensors, a.chunks, a.n_trained_chunks, a.scale, a.scaling_enabled,
-                                                 partial, flags);
+                                                 w.partial, w.flags);
     S2A_LAUNCH_CHECK();
   }
   FinaliseArgs f;
-  f.partial = partial;
-  f.flags = flags;
+  f.partial = w.partial;
+  f.flags = w.flags;
   f.n_partials = need_norm ? a.n_trained_chunks : 0;
   f.scale = a.scale;
   f.counters = a.counters;
@@ -345,13 +346,13 @@ extern "C" int s2a_train_update(const s2a_train_update_args* args, void* workspa
   f.backoff = a.backoff_factor;
   f.ema_decay = a.ema_decay;
   f.ema_tau = a.ema_tau;
-  f.ctrl = ctrl;
+  f.ctrl = w.ctrl;
   f.stats = a.stats;
   k_optim_finalise<<<1, kThreads, 0, st>>>(f);
   S2A_LAUNCH_CHECK();
   if (a.n_chunks > 0) {
     const int grid = (int)(a.n_chunks < kMaxGrid ? a.n_chunks : kMaxGrid);
-    k_optim_apply<<<grid, kThreads, 0, st>>>(a.tensors, a.chunks, a.n_chunks, a.lr, a.hyper, ctrl);
+    k_optim_apply<<<grid, kThreads, 0, st>>>(a.tensors, a.chunks, a.n_chunks, a.lr, a.hyper, w.ctrl);
     S2A_LAUNCH_CHECK();
   }
   return S2A_OK;

@@ -559,13 +559,81 @@ static size_t poly_pair_cap(int64_t n) {
   return std::min(all, std::max<size_t>((size_t)n * 32, (size_t)1 << 20)) + 1;
 }
 
+// The ten buffers both f64 NMS forms sort, mask and scan with, in carve order (Box: PolyBox / RBox6)
+template <typename Box>
+struct Nms64Ws {
+  unsigned long long *key_a, *key_b; int32_t *idx_a, *order; Box* sorted; unsigned long long* mask; uint8_t *keep_orig, *flags;
+  unsigned long long* small;   // seg_start[2] | num_seg | nblk | mask_off[2] | status; [16], [17]: the list form's pair / edge count
+  void* rp; size_t rpb;        // rocPRIM scratch (sort, select), its bytes
+  uint32_t* seg_start() const { return reinterpret_cast<uint32_t*>(small); }
+  uint32_t* num_seg() const { return seg_start() + 4; }
+  uint32_t* nblk() const { return seg_start() + 6; }
+  uint32_t* status() const { return seg_start() + 8; }
+  unsigned long long* mask_off() const { return small + 8; }
+};
+template <typename Box>
+static bool carve(Carver& cv, int64_t n, Nms64Ws<Box>& w) {
+  const size_t sz = (size_t)n, nb = (sz + 63) / 64;
+  w.key_a = cv.take<unsigned long long>(sz);
+  w.key_b = cv.take<unsigned long long>(sz);
+  w.idx_a = cv.take<int32_t>(sz);
+  w.order = cv.take<int32_t>(sz);
+  w.sorted = cv.take<Box>(sz);
+  w.mask = cv.take<unsigned long long>(sz * nb);
+  w.keep_orig = cv.take<uint8_t>(sz);
+  w.flags = cv.take<uint8_t>(sz);
+  w.small = cv.take<unsigned long long>(64);
+  w.rpb = sz * 40 + (8u << 20);
+  w.rp = cv.take<char>(w.rpb);
+  return cv.ok();
+}
+// the polygon form's list path behind them
+struct PolyNmsWs : Nms64Ws<PolyBox> {
+  uint2 *pairs, *edges, *alive; void* rounds_ws; uint32_t* cnt_scratch;   // [cap] each, rounds_bytes, keep_compact_scratch_words()
+  size_t cap, rounds_bytes;
+};
+static bool carve(Carver& cv, int64_t n, PolyNmsWs& w) {
+  carve<PolyBox>(cv, n, w);
+  w.cap = poly_pair_cap(n);
+  w.pairs = cv.take<uint2>(w.cap);
+  w.edges = cv.take<uint2>(w.cap);
+  w.alive = cv.take<uint2>(w.cap);
+  w.rounds_bytes = nms_edge_rounds_workspace(n);
+  w.rounds_ws = cv.take<char>(w.rounds_bytes);
+  w.cnt_scratch = cv.take<uint32_t>(keep_compact_scratch_words());
+  return cv.ok();
+}
+constexpr size_t kNms64WsSlack = 8192 - 512;   // the 8192 both queries always added, less `small`, which the carve now counts; headroom only
+
+// the mask form's tail: greedy scan over the mask -> flags in score order -> rocprim::select of the kept rows into keep[] /
+// *count_dev -> the host's copy of the count, when asked for
+template <typename Box>
+static int nms64_scan_select(const char* who, const Nms64Ws<Box>& w, int64_t n, int64_t* keep, int64_t* count_dev,
+                             int64_t* host_count, hipStream_t st) {
+  const size_t sz = (size_t)n, nb = (sz + 63) / 64;
+  int rc = launch_nms_scan(w.mask, w.seg_start(), w.num_seg(), w.mask_off(), w.nblk(), w.order, w.keep_orig, (uint32_t)nb,
+                           w.mask_off() + 1, (unsigned long long)sz * nb, w.status(), st);
+  if (rc != S2A_OK) return rc;
+  k_poly_flags<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(w.keep_orig, w.order, n, w.flags);
+  size_t need = 0;
+  S2A_HIP(rocprim::select(nullptr, need, w.order, w.flags, keep, count_dev, sz, st));
+  if (need > w.rpb) {
+    set_error("%s: workspace too small (select scratch %zu < %zu bytes)", who, w.rpb, need);
+    return S2A_EWORKSPACE;
+  }
+  S2A_HIP(rocprim::select(w.rp, need, w.order, w.flags, keep, count_dev, sz, st));
+  S2A_LAUNCH_CHECK();
+  if (host_count) {
+    S2A_HIP(hipMemcpyAsync(host_count, count_dev, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    S2A_HIP(hipStreamSynchronize(st));
+  }
+  return S2A_OK;
+}
+
 extern "C" size_t s2a_nms_poly_workspace_bytes(int64_t n) {
   if (n < 0 || n >= (1ll << 31)) return 0;   // (sizes the entry point refuses)
   if (n == 0) return 256;
-  size_t sz = (size_t)n, nb = (sz + 63) / 64;
-  return align_up(sz * 8) * 2 + align_up(sz * 4) * 2 + align_up(sz * sizeof(PolyBox)) + align_up(sz * nb * 8) +
-         align_up(sz) * 2 + align_up(sz * 40 + (8u << 20)) + align_up(poly_pair_cap(n) * 8) * 3 +
-         nms_edge_rounds_workspace(n) + align_up(keep_compact_scratch_words() * 4) + 8192;
+  return carved_bytes<PolyNmsWs>(n) + kNms64WsSlack;
 }
 
 extern "C" int s2a_nms_poly(const double* dets9, int64_t n, double thresh, int64_t* keep, int64_t* count_dev,
@@ -582,64 +650,38 @@ extern "C" int s2a_nms_poly(const double* dets9, int64_t n, double thresh, int64
   S2A_CHECK_ARG(dets9 && keep, "nms_poly: NULL tensor");
   const size_t sz = (size_t)n, nb = (sz + 63) / 64;
   S2A_CHECK_ARG(nb <= 65535, "nms_poly: more than 4.19 M boxes is not supported");
-  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, s2a_nms_poly_workspace_bytes(n), "nms_poly");
-  Carver cv(workspace, workspace_bytes);
-  auto* key_a = cv.take<unsigned long long>(sz);
-  auto* key_b = cv.take<unsigned long long>(sz);
-  auto* idx_a = cv.take<int32_t>(sz);
-  auto* order = cv.take<int32_t>(sz);
-  auto* sorted = cv.take<PolyBox>(sz);
-  auto* mask = cv.take<unsigned long long>(sz * nb);
-  auto* keep_orig = cv.take<uint8_t>(sz);
-  auto* flags = cv.take<uint8_t>(sz);
-  auto* small = cv.take<unsigned long long>(64);   // seg_start[2] | num_seg | nblk | mask_off[2] | status
-  size_t rpb = sz * 40 + (8u << 20);
-  void* rp = cv.take<char>(rpb);
-  const size_t cap = poly_pair_cap(n);
-  auto* pairs = cv.take<uint2>(cap);
-  auto* edges = cv.take<uint2>(cap);
-  auto* alive = cv.take<uint2>(cap);
-  const size_t rounds_bytes = nms_edge_rounds_workspace(n);
-  void* rounds_ws = cv.take<char>(rounds_bytes);
-  auto* cnt_scratch = cv.take<uint32_t>(keep_compact_scratch_words());
-  if (!rp || !small || !pairs || !edges || !alive || !rounds_ws || !cnt_scratch || cv.off > workspace_bytes) {
-    set_error("nms_poly: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-    return S2A_EWORKSPACE;
-  }
-  uint32_t* seg_start = reinterpret_cast<uint32_t*>(small);
-  uint32_t* num_seg = seg_start + 4;
-  uint32_t* nblk = seg_start + 6;
-  uint32_t* status = seg_start + 8;
-  unsigned long long* mask_off = small + 8;
+  PolyNmsWs w;
+  if (int rc = carve_workspace(workspace, workspace_bytes, w, kNms64WsSlack, "nms_poly", n)) return rc;
+  const size_t cap = w.cap;
   const unsigned g = (unsigned)((n + 255) / 256);
-  S2A_HIP(hipMemsetAsync(small, 0, 64 * 8, st));
-  S2A_HIP(hipMemsetAsync(keep_orig, 0, sz, st));
-  k_poly_keys<<<g, 256, 0, st>>>(dets9, n, key_a, idx_a);
+  S2A_HIP(hipMemsetAsync(w.small, 0, 64 * 8, st));
+  S2A_HIP(hipMemsetAsync(w.keep_orig, 0, sz, st));
+  k_poly_keys<<<g, 256, 0, st>>>(dets9, n, w.key_a, w.idx_a);
   size_t need = 0;
-  S2A_HIP(rocprim::radix_sort_pairs(nullptr, need, key_a, key_b, idx_a, order, sz, 0, 64, st));
-  if (need > rpb) {
-    set_error("nms_poly: workspace too small (sort scratch %zu < %zu bytes)", rpb, need);
+  S2A_HIP(rocprim::radix_sort_pairs(nullptr, need, w.key_a, w.key_b, w.idx_a, w.order, sz, 0, 64, st));
+  if (need > w.rpb) {
+    set_error("nms_poly: workspace too small (sort scratch %zu < %zu bytes)", w.rpb, need);
     return S2A_EWORKSPACE;
   }
-  S2A_HIP(rocprim::radix_sort_pairs(rp, need, key_a, key_b, idx_a, order, sz, 0, 64, st));
-  k_poly_prep<<<g, 256, 0, st>>>(dets9, order, n, sorted, seg_start, num_seg, mask_off, nblk);
+  S2A_HIP(rocprim::radix_sort_pairs(w.rp, need, w.key_a, w.key_b, w.idx_a, w.order, sz, 0, 64, st));
+  k_poly_prep<<<g, 256, 0, st>>>(dets9, w.order, n, w.sorted, w.seg_start(), w.num_seg(), w.mask_off(), w.nblk());
   dim3 grid((unsigned)nb, (unsigned)nb);
   // LIST form (round 6; a synchronous caller, thresh >= 0): HBB pair list -> polyiou on the listed pairs -> suppression EDGES
   // -> the greedy resolve by rounds the rotated NMS uses -> compaction.  No N x N / 64 mask, no serial scan (2.1 ms at
   // 20 000 boxes), no library select.  The host reads the pair count with the keep count: a pair list that overflowed (dense
   // scenes) sends the call through the mask form below.  S2A_POLY_NMS_LIST=0: the mask form always (A/B, tests)
   const char* e_list = getenv("S2A_POLY_NMS_LIST");
+  unsigned long long* pair_count = w.small + 16;
   if (thresh >= 0 && host_count && !(e_list && e_list[0] == '0')) {
-    unsigned long long* pair_count = small + 16;
-    unsigned long long* edge_count = small + 17;
-    k_poly_cull<<<dim3((unsigned)((n + kCullCols - 1) / kCullCols), (unsigned)((n + 255) / 256)), 256, 0, st>>>(sorted, n, pairs, pair_count, (unsigned long long)cap, thresh);
+    unsigned long long* edge_count = w.small + 17;
+    k_poly_cull<<<dim3((unsigned)((n + kCullCols - 1) / kCullCols), (unsigned)((n + 255) / 256)), 256, 0, st>>>(w.sorted, n, w.pairs, pair_count, (unsigned long long)cap, thresh);
     const unsigned hb = (unsigned)std::min<size_t>((cap + kPolyThreads - 1) / kPolyThreads, 256 * 16);
-    k_poly_edges<<<hb, kPolyThreads, 0, st>>>(sorted, pairs, pair_count, (unsigned long long)cap, thresh, edges, edge_count);
+    k_poly_edges<<<hb, kPolyThreads, 0, st>>>(w.sorted, w.pairs, pair_count, (unsigned long long)cap, thresh, w.edges, edge_count);
     S2A_LAUNCH_CHECK();
-    int rcl = launch_nms_edge_rounds(edges, (unsigned long long)cap, edge_count, alive, (unsigned long long)cap, n, order, keep_orig,
-                                     rounds_ws, rounds_bytes, st);
+    int rcl = launch_nms_edge_rounds(w.edges, (unsigned long long)cap, edge_count, w.alive, (unsigned long long)cap, n, w.order,
+                                     w.keep_orig, w.rounds_ws, w.rounds_bytes, st);
     if (rcl != S2A_OK) return rcl;
-    rcl = launch_keep_compact(keep_orig, order, n, cnt_scratch, keep, count_dev, st);
+    rcl = launch_keep_compact(w.keep_orig, w.order, n, w.cnt_scratch, keep, count_dev, st);
     if (rcl != S2A_OK) return rcl;
     unsigned long long host_pairs = 0;
     S2A_HIP(hipMemcpyAsync(&host_pairs, pair_count, sizeof(host_pairs), hipMemcpyDeviceToHost, st));
@@ -647,45 +689,26 @@ extern "C" int s2a_nms_poly(const double* dets9, int64_t n, double thresh, int64
     S2A_HIP(hipStreamSynchronize(st));
     if (host_pairs <= (unsigned long long)cap) return S2A_OK;
     // the pair list overflowed: the mask form settles the call (its own zero-fills first)
-    S2A_HIP(hipMemsetAsync(small + 16, 0, 16, st));
-    S2A_HIP(hipMemsetAsync(keep_orig, 0, sz, st));
+    S2A_HIP(hipMemsetAsync(w.small + 16, 0, 16, st));
+    S2A_HIP(hipMemsetAsync(w.keep_orig, 0, sz, st));
   }
   if (thresh >= 0) {
-    unsigned long long* pair_count = small + 16;
-    S2A_HIP(hipMemsetAsync(mask, 0, sz * nb * 8, st));
-    k_poly_cull<<<dim3((unsigned)((n + kCullCols - 1) / kCullCols), (unsigned)((n + 255) / 256)), 256, 0, st>>>(sorted, n, pairs, pair_count, (unsigned long long)cap, -1.0);
+    S2A_HIP(hipMemsetAsync(w.mask, 0, sz * nb * 8, st));
+    k_poly_cull<<<dim3((unsigned)((n + kCullCols - 1) / kCullCols), (unsigned)((n + 255) / 256)), 256, 0, st>>>(w.sorted, n, w.pairs, pair_count, (unsigned long long)cap, -1.0);
     const unsigned hb = (unsigned)std::min<size_t>((cap + kPolyThreads - 1) / kPolyThreads, 256 * 16);
-    k_poly_heavy<<<hb, kPolyThreads, 0, st>>>(sorted, pairs, pair_count, (unsigned long long)cap, thresh, (uint32_t)nb, mask);
-    k_poly_mask<<<grid, 64, 0, st>>>(sorted, n, thresh, mask, pair_count, (unsigned long long)cap);   // overflow only
+    k_poly_heavy<<<hb, kPolyThreads, 0, st>>>(w.sorted, w.pairs, pair_count, (unsigned long long)cap, thresh, (uint32_t)nb, w.mask);
+    k_poly_mask<<<grid, 64, 0, st>>>(w.sorted, n, thresh, w.mask, pair_count, (unsigned long long)cap);   // overflow only
   } else {
-    k_poly_mask<<<grid, 64, 0, st>>>(sorted, n, thresh, mask, nullptr, 0);
+    k_poly_mask<<<grid, 64, 0, st>>>(w.sorted, n, thresh, w.mask, nullptr, 0);
   }
   S2A_LAUNCH_CHECK();
-  int rc = launch_nms_scan(mask, seg_start, num_seg, mask_off, nblk, order, keep_orig, (uint32_t)nb, mask_off + 1,
-                           (unsigned long long)sz * nb, status, st);
-  if (rc != S2A_OK) return rc;
-  k_poly_flags<<<g, 256, 0, st>>>(keep_orig, order, n, flags);
-  need = 0;
-  S2A_HIP(rocprim::select(nullptr, need, order, flags, keep, count_dev, sz, st));
-  if (need > rpb) {
-    set_error("nms_poly: workspace too small (select scratch %zu < %zu bytes)", rpb, need);
-    return S2A_EWORKSPACE;
-  }
-  S2A_HIP(rocprim::select(rp, need, order, flags, keep, count_dev, sz, st));
-  S2A_LAUNCH_CHECK();
-  if (host_count) {
-    S2A_HIP(hipMemcpyAsync(host_count, count_dev, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    S2A_HIP(hipStreamSynchronize(st));
-  }
-  return S2A_OK;
+  return nms64_scan_select("nms_poly", w, n, keep, count_dev, host_count, st);
 }
 
 extern "C" size_t s2a_nms_rotated_f64_workspace_bytes(int64_t n) {
   if (n < 0 || n >= (1ll << 31)) return 0;   // (sizes the entry point refuses)
   if (n == 0) return 256;
-  size_t sz = (size_t)n, nb = (sz + 63) / 64;
-  return align_up(sz * 8) * 2 + align_up(sz * 4) * 2 + align_up(sz * sizeof(RBox6)) + align_up(sz * nb * 8) +
-         align_up(sz) * 2 + align_up(sz * 40 + (8u << 20)) + 8192;
+  return carved_bytes<Nms64Ws<RBox6>>(n) + kNms64WsSlack;
 }
 
 extern "C" int s2a_nms_rotated_f64(const double* dets5, const double* scores, const double* labels, int64_t n,
@@ -703,57 +726,21 @@ extern "C" int s2a_nms_rotated_f64(const double* dets5, const double* scores, co
   S2A_CHECK_ARG(dets5 && scores && keep, "nms_rotated_f64: NULL tensor");
   const size_t sz = (size_t)n, nb = (sz + 63) / 64;
   S2A_CHECK_ARG(nb <= 65535 && sz * nb * 8 < (8ull << 30), "nms_rotated_f64: more than 260 k boxes is not supported (N x N/64 mask)");
-  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, s2a_nms_rotated_f64_workspace_bytes(n), "nms_rotated_f64");
-  Carver cv(workspace, workspace_bytes);
-  auto* key_a = cv.take<unsigned long long>(sz);
-  auto* key_b = cv.take<unsigned long long>(sz);
-  auto* idx_a = cv.take<int32_t>(sz);
-  auto* order = cv.take<int32_t>(sz);
-  auto* sorted = cv.take<RBox6>(sz);
-  auto* mask = cv.take<unsigned long long>(sz * nb);
-  auto* keep_orig = cv.take<uint8_t>(sz);
-  auto* flags = cv.take<uint8_t>(sz);
-  auto* small = cv.take<unsigned long long>(64);
-  size_t rpb = sz * 40 + (8u << 20);
-  void* rp = cv.take<char>(rpb);
-  if (!rp || !small || cv.off > workspace_bytes) {
-    set_error("nms_rotated_f64: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-    return S2A_EWORKSPACE;
-  }
-  uint32_t* seg_start = reinterpret_cast<uint32_t*>(small);
-  uint32_t* num_seg = seg_start + 4;
-  uint32_t* nblk = seg_start + 6;
-  uint32_t* status = seg_start + 8;
-  unsigned long long* mask_off = small + 8;
+  Nms64Ws<RBox6> w;
+  if (int rc = carve_workspace(workspace, workspace_bytes, w, kNms64WsSlack, "nms_rotated_f64", n)) return rc;
   const unsigned g = (unsigned)((n + 255) / 256);
-  S2A_HIP(hipMemsetAsync(small, 0, 64 * 8, st));
-  S2A_HIP(hipMemsetAsync(keep_orig, 0, sz, st));
-  k_rot64_keys<<<g, 256, 0, st>>>(scores, n, key_a, idx_a);
+  S2A_HIP(hipMemsetAsync(w.small, 0, 64 * 8, st));
+  S2A_HIP(hipMemsetAsync(w.keep_orig, 0, sz, st));
+  k_rot64_keys<<<g, 256, 0, st>>>(scores, n, w.key_a, w.idx_a);
   size_t need = 0;
-  S2A_HIP(rocprim::radix_sort_pairs(nullptr, need, key_a, key_b, idx_a, order, sz, 0, 64, st));
-  if (need > rpb) {
-    set_error("nms_rotated_f64: workspace too small (sort scratch %zu < %zu bytes)", rpb, need);
+  S2A_HIP(rocprim::radix_sort_pairs(nullptr, need, w.key_a, w.key_b, w.idx_a, w.order, sz, 0, 64, st));
+  if (need > w.rpb) {
+    set_error("nms_rotated_f64: workspace too small (sort scratch %zu < %zu bytes)", w.rpb, need);
     return S2A_EWORKSPACE;
   }
-  S2A_HIP(rocprim::radix_sort_pairs(rp, need, key_a, key_b, idx_a, order, sz, 0, 64, st));
-  k_rot64_prep<<<g, 256, 0, st>>>(dets5, labels, order, n, sorted, seg_start, num_seg, mask_off, nblk);
-  k_rot64_mask<<<dim3((unsigned)nb, (unsigned)nb), 64, 0, st>>>(sorted, n, iou_threshold, mask);
+  S2A_HIP(rocprim::radix_sort_pairs(w.rp, need, w.key_a, w.key_b, w.idx_a, w.order, sz, 0, 64, st));
+  k_rot64_prep<<<g, 256, 0, st>>>(dets5, labels, w.order, n, w.sorted, w.seg_start(), w.num_seg(), w.mask_off(), w.nblk());
+  k_rot64_mask<<<dim3((unsigned)nb, (unsigned)nb), 64, 0, st>>>(w.sorted, n, iou_threshold, w.mask);
   S2A_LAUNCH_CHECK();
-  int rc = launch_nms_scan(mask, seg_start, num_seg, mask_off, nblk, order, keep_orig, (uint32_t)nb, mask_off + 1,
-                           (unsigned long long)sz * nb, status, st);
-  if (rc != S2A_OK) return rc;
-  k_poly_flags<<<g, 256, 0, st>>>(keep_orig, order, n, flags);
-  need = 0;
-  S2A_HIP(rocprim::select(nullptr, need, order, flags, keep, count_dev, sz, st));
-  if (need > rpb) {
-    set_error("nms_rotated_f64: workspace too small (select scratch %zu < %zu bytes)", rpb, need);
-    return S2A_EWORKSPACE;
-  }
-  S2A_HIP(rocprim::select(rp, need, order, flags, keep, count_dev, sz, st));
-  S2A_LAUNCH_CHECK();
-  if (host_count) {
-    S2A_HIP(hipMemcpyAsync(host_count, count_dev, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    S2A_HIP(hipStreamSynchronize(st));
-  }
-  return S2A_OK;
+  return nms64_scan_select("nms_rotated_f64", w, n, keep, count_dev, host_count, st);
 }

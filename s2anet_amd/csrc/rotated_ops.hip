@@ -3231,28 +3231,30 @@ __global__ void k_edge_rounds_init(EdgeRoundsWs* __restrict__ W, uint8_t* __rest
     W->num_seg = 1u;
   }
 }
+struct EdgeRoundsBufs { EdgeRoundsWs* W; uint8_t *state, *blocked; };   // carved from the workspace, in this order
+bool carve(Carver& cv, int64_t n, EdgeRoundsBufs& b) {
+  b.W = cv.take<EdgeRoundsWs>(1);
+  b.state = cv.take<uint8_t>((size_t)n);
+  b.blocked = cv.take<uint8_t>(2 * (size_t)n);
+  return cv.ok();
+}
+constexpr size_t kEdgeRoundsWsSlack = 256;   // headroom the query has always declared; no sub-buffer lives in it
 }  // namespace
 size_t nms_edge_rounds_workspace(int64_t n) {
-  return align_up(sizeof(EdgeRoundsWs)) + align_up((size_t)n) + align_up(2 * (size_t)n) + 256;
+  return carved_bytes<EdgeRoundsBufs>(n) + kEdgeRoundsWsSlack;
 }
 int launch_nms_edge_rounds(uint2* edges, unsigned long long edge_cap, const unsigned long long* edge_count_dev, uint2* alive_list,
                            unsigned long long alive_cap, int64_t n, const int32_t* order, uint8_t* keep_orig, void* workspace,
                            size_t workspace_bytes, hipStream_t st) {
   S2A_CHECK_ARG(n > 0 && n < (1ll << 31), "nms edge rounds: n out of range");
-  Carver cv(workspace, workspace_bytes);
-  auto* W = cv.take<EdgeRoundsWs>(1);
-  auto* state = cv.take<uint8_t>((size_t)n);
-  auto* blocked = cv.take<uint8_t>(2 * (size_t)n);
-  if (!W || !state || !blocked) {
-    set_error("nms edge rounds: workspace too small (%zu < %zu bytes)", workspace_bytes, cv.off);
-    return S2A_EWORKSPACE;
-  }
-  k_edge_rounds_init<<<grid_for(n), 256, 0, st>>>(W, state, blocked, n, edge_count_dev);
+  EdgeRoundsBufs b;
+  if (int rc = carve_workspace(workspace, workspace_bytes, b, kEdgeRoundsWsSlack, "nms edge rounds", n)) return rc;
+  k_edge_rounds_init<<<grid_for(n), 256, 0, st>>>(b.W, b.state, b.blocked, n, edge_count_dev);
   for (int r = 1; r <= kNmsRounds; r++)
-    k_nms_round<<<256, kThreads, 0, st>>>(edges, &W->C, edge_cap, state, blocked, n, r, r == kNmsRounds ? alive_list : nullptr, alive_cap);
-  k_nms_finish_segments<<<1, kFinThreads, 0, st>>>(&W->C, W->seg_start, &W->num_seg, alive_list, alive_cap, edges, edge_cap, state,
-                                                   blocked, n, nullptr, 0, 0u, 0, 0);
-  k_nms_finish<<<grid_for(n), 256, 0, st>>>(state, blocked, &W->C, order, nullptr, nullptr, n, keep_orig);
+    k_nms_round<<<256, kThreads, 0, st>>>(edges, &b.W->C, edge_cap, b.state, b.blocked, n, r, r == kNmsRounds ? alive_list : nullptr, alive_cap);
+  k_nms_finish_segments<<<1, kFinThreads, 0, st>>>(&b.W->C, b.W->seg_start, &b.W->num_seg, alive_list, alive_cap, edges, edge_cap, b.state,
+                                                   b.blocked, n, nullptr, 0, 0u, 0, 0);
+  k_nms_finish<<<grid_for(n), 256, 0, st>>>(b.state, b.blocked, &b.W->C, order, nullptr, nullptr, n, keep_orig);
   S2A_LAUNCH_CHECK();
   return S2A_OK;
 }
@@ -3391,13 +3393,19 @@ __global__ void k_gather_candidates(const float* __restrict__ boxes5, const floa
   ogrp[i] = valid ? img : -1;
   ocls[i] = valid ? cls : -1;
 }
+struct CandWs { int32_t* sel; uint32_t* blk; };   // carved from the workspace, in this order: [total], [blocks + 1]
+bool carve(Carver& cv, int64_t total, CandWs& w) {
+  w.sel = cv.take<int32_t>((size_t)total);
+  w.blk = cv.take<uint32_t>((size_t)((total + kCandBlock - 1) / kCandBlock) + 1);
+  return cv.ok();
+}
+constexpr size_t kCandWsSlack = 1024;   // headroom the query has always declared; no sub-buffer lives in it
 }  // namespace
 }  // namespace s2a
 
 extern "C" size_t s2a_multiclass_candidates_workspace_bytes(int64_t total) {
   if (total < 0 || total >= (1ll << 31)) return 0;   // (sizes the entry point refuses)
-  const size_t t = (size_t)std::max<int64_t>(total, 1);
-  return align_up(t * 4) + align_up(((t + kCandBlock - 1) / kCandBlock + 1) * 4) + 1024;
+  return carved_bytes<CandWs>(std::max<int64_t>(total, 1)) + kCandWsSlack;
 }
 
 extern "C" int s2a_multiclass_candidates(const float* boxes, const float* scores, int64_t batch,
@@ -3417,20 +3425,14 @@ extern "C" int s2a_multiclass_candidates(const float* boxes, const float* scores
     return S2A_OK;
   }
   S2A_CHECK_ARG(boxes && scores, "multiclass_candidates: NULL input");
-  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, s2a_multiclass_candidates_workspace_bytes(total), "multiclass_candidates");
-  Carver cv(workspace, workspace_bytes);
+  CandWs w;
+  if (int rc = carve_workspace(workspace, workspace_bytes, w, kCandWsSlack, "multiclass_candidates", total)) return rc;
   const int64_t nb = (total + kCandBlock - 1) / kCandBlock;
-  int32_t* sel = cv.take<int32_t>((size_t)total);
-  uint32_t* blk = cv.take<uint32_t>((size_t)nb + 1);
-  if (!sel || !blk) {
-    set_error("multiclass_candidates: workspace too small (%zu bytes)", workspace_bytes);
-    return S2A_EWORKSPACE;
-  }
-  k_cand_count<<<(unsigned)nb, 256, 0, st>>>(scores, score_thr, total, blk);
-  k_cand_scan<<<1, 1024, 0, st>>>(blk, nb, reinterpret_cast<unsigned long long*>(count_dev));
-  k_cand_scatter<<<(unsigned)nb, 256, 0, st>>>(scores, score_thr, total, blk, sel);
+  k_cand_count<<<(unsigned)nb, 256, 0, st>>>(scores, score_thr, total, w.blk);
+  k_cand_scan<<<1, 1024, 0, st>>>(w.blk, nb, reinterpret_cast<unsigned long long*>(count_dev));
+  k_cand_scatter<<<(unsigned)nb, 256, 0, st>>>(scores, score_thr, total, w.blk, w.sel);
   k_gather_candidates<<<(unsigned)((cap + 255) / 256), 256, 0, st>>>(
-      boxes, scores, sel, reinterpret_cast<const unsigned long long*>(count_dev), cap, (int)n,
+      boxes, scores, w.sel, reinterpret_cast<const unsigned long long*>(count_dev), cap, (int)n,
       (int)num_classes, out_boxes, out_scores, out_seg, out_grp, out_cls);
   S2A_LAUNCH_CHECK();
   return S2A_OK;

@@ -334,6 +334,36 @@ size_t scene_pair_cap(int64_t n, int64_t pair_capacity) {
 }
 constexpr int kMaxClasses = 1024;
 size_t scene_sort_scratch(size_t n) { return n * 40 + (8u << 20); }
+struct MergeWs {                          // carved from the workspace, in this order
+  unsigned long long *key_a, *key_s; int32_t *idx_a, *order; float* polys32; PolyBox* sorted; uint8_t* keep_orig;   // [n] ([n * 8])
+  MergeCtl* ctl; uint32_t *seg_start, *cnt;            // 1, [kMaxClasses + 2], [n / kOutRows, rounded up]
+  void* rp; uint2 *pairs, *edges, *alive;              // rocPRIM sort scratch of rpb bytes; [cap] each
+  void* rounds_ws;                                     // launch_nms_edge_rounds' own, rounds_bytes
+  size_t rpb, cap, rounds_bytes;
+};
+bool carve(Carver& cv, int64_t n, int64_t pair_capacity, MergeWs& w) {
+  const size_t sz = (size_t)n;
+  w.key_a = cv.take<unsigned long long>(sz);
+  w.key_s = cv.take<unsigned long long>(sz);
+  w.idx_a = cv.take<int32_t>(sz);
+  w.order = cv.take<int32_t>(sz);
+  w.polys32 = cv.take<float>(sz * 8);
+  w.sorted = cv.take<PolyBox>(sz);
+  w.keep_orig = cv.take<uint8_t>(sz);
+  w.ctl = cv.take<MergeCtl>(1);
+  w.seg_start = cv.take<uint32_t>(kMaxClasses + 2);
+  w.cnt = cv.take<uint32_t>((sz + kOutRows - 1) / kOutRows);
+  w.rpb = scene_sort_scratch(sz);
+  w.rp = cv.take<char>(w.rpb);
+  w.cap = scene_pair_cap(n, pair_capacity);
+  w.pairs = cv.take<uint2>(w.cap);
+  w.edges = cv.take<uint2>(w.cap);
+  w.alive = cv.take<uint2>(w.cap);
+  w.rounds_bytes = nms_edge_rounds_workspace(n);
+  w.rounds_ws = cv.take<char>(w.rounds_bytes);
+  return cv.ok();
+}
+constexpr size_t kMergeWsSlack = 4096;   // headroom the query has always declared; no sub-buffer lives in it
 
 }  // namespace
 }  // namespace s2a
@@ -358,10 +388,7 @@ extern "C" int s2a_scene_gather_u8(const uint8_t* scene, int64_t height, int64_t
 extern "C" size_t s2a_scene_merge_workspace_bytes(int64_t n_rows, int64_t pair_capacity) {
   if (n_rows < 0 || n_rows >= (1ll << 31)) return 0;   // (sizes the entry point refuses)
   if (n_rows == 0) return 256;
-  const size_t sz = (size_t)n_rows, cap = scene_pair_cap(n_rows, pair_capacity);
-  return align_up(sz * 8) * 2 + align_up(sz * 4) * 2 + align_up(sz * 32) + align_up(sz * sizeof(PolyBox)) + align_up(sz) +
-         align_up(sizeof(MergeCtl)) + align_up((kMaxClasses + 2) * 4) + align_up(((sz + kOutRows - 1) / kOutRows) * 4) +
-         align_up(scene_sort_scratch(sz)) + align_up(cap * 8) * 3 + align_up(nms_edge_rounds_workspace(n_rows)) + 4096;
+  return carved_bytes<MergeWs>(n_rows, pair_capacity) + kMergeWsSlack;
 }
 
 extern "C" int s2a_scene_merge(const float* dets, const int32_t* labels, const int32_t* counts, const int32_t* origins,
@@ -382,56 +409,34 @@ extern "C" int s2a_scene_merge(const float* dets, const int32_t* labels, const i
     return S2A_OK;
   }
   S2A_CHECK_ARG(dets && labels && counts && origins && out_polys && out_scores && out_labels && out_src, "scene_merge: NULL tensor");
-  S2A_CHECK_WORKSPACE(workspace, workspace_bytes, s2a_scene_merge_workspace_bytes(n, pair_capacity), "scene_merge");
-  const size_t sz = (size_t)n, cap = scene_pair_cap(n, pair_capacity);
+  MergeWs w;
+  if (int rc = carve_workspace(workspace, workspace_bytes, w, kMergeWsSlack, "scene_merge", n, pair_capacity)) return rc;
+  const size_t sz = (size_t)n, cap = w.cap;
   const int nb = (int)((sz + kOutRows - 1) / kOutRows);
-  Carver cv(workspace, workspace_bytes);
-  auto* key_a = cv.take<unsigned long long>(sz);
-  auto* key_s = cv.take<unsigned long long>(sz);
-  auto* idx_a = cv.take<int32_t>(sz);
-  auto* order = cv.take<int32_t>(sz);
-  auto* polys32 = cv.take<float>(sz * 8);
-  auto* sorted = cv.take<PolyBox>(sz);
-  auto* keep_orig = cv.take<uint8_t>(sz);
-  auto* ctl = cv.take<MergeCtl>(1);
-  auto* seg_start = cv.take<uint32_t>(kMaxClasses + 2);
-  auto* cnt = cv.take<uint32_t>((size_t)nb);
-  const size_t rpb = scene_sort_scratch(sz);
-  void* rp = cv.take<char>(rpb);
-  auto* pairs = cv.take<uint2>(cap);
-  auto* edges = cv.take<uint2>(cap);
-  auto* alive = cv.take<uint2>(cap);
-  const size_t rounds_bytes = nms_edge_rounds_workspace(n);
-  void* rounds_ws = cv.take<char>(rounds_bytes);
-  if (!key_a || !key_s || !idx_a || !order || !polys32 || !sorted || !keep_orig || !ctl || !seg_start || !cnt || !rp || !pairs ||
-      !edges || !alive || !rounds_ws) {
-    set_error("scene_merge: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-    return S2A_EWORKSPACE;
-  }
   const unsigned g = (unsigned)((std::max<int64_t>(n, num_classes) + 255) / 256);
-  k_scene_keys<<<g, 256, 0, st>>>(dets, labels, counts, n, (int32_t)K, num_classes, key_a, idx_a, ctl,
+  k_scene_keys<<<g, 256, 0, st>>>(dets, labels, counts, n, (int32_t)K, num_classes, w.key_a, w.idx_a, w.ctl,
                                   reinterpret_cast<long long*>(class_counts));
   size_t need = 0;
-  S2A_HIP(rocprim::radix_sort_pairs(nullptr, need, key_a, key_s, idx_a, order, sz, 0, 48, st));
-  if (need > rpb) {
-    set_error("scene_merge: workspace too small (sort scratch %zu < %zu bytes)", rpb, need);
+  S2A_HIP(rocprim::radix_sort_pairs(nullptr, need, w.key_a, w.key_s, w.idx_a, w.order, sz, 0, 48, st));
+  if (need > w.rpb) {
+    set_error("scene_merge: workspace too small (sort scratch %zu < %zu bytes)", w.rpb, need);
     return S2A_EWORKSPACE;
   }
-  S2A_HIP(rocprim::radix_sort_pairs(rp, need, key_a, key_s, idx_a, order, sz, 0, 48, st));
-  int rc = s2a_rbox_to_poly(dets, n, 6, polys32, stream);
+  S2A_HIP(rocprim::radix_sort_pairs(w.rp, need, w.key_a, w.key_s, w.idx_a, w.order, sz, 0, 48, st));
+  int rc = s2a_rbox_to_poly(dets, n, 6, w.polys32, stream);
   if (rc != S2A_OK) return rc;
-  k_scene_prep<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(key_s, order, polys32, origins, rates, n, (int32_t)K, num_classes, sorted,
-                                                            seg_start);
+  k_scene_prep<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(w.key_s, w.order, w.polys32, origins, rates, n, (int32_t)K, num_classes, w.sorted,
+                                                            w.seg_start);
   k_scene_cull<<<dim3((unsigned)((n + kSceneCols - 1) / kSceneCols), (unsigned)((n + 255) / 256)), 256, 0, st>>>(
-      sorted, key_s, seg_start, num_classes, pairs, ctl, (unsigned long long)cap);
+      w.sorted, w.key_s, w.seg_start, num_classes, w.pairs, w.ctl, (unsigned long long)cap);
   const unsigned hb = (unsigned)std::min<size_t>((cap + kPolyThreads - 1) / kPolyThreads, 256 * 16);
-  k_poly_edges<<<hb, kPolyThreads, 0, st>>>(sorted, pairs, &ctl->pairs, (unsigned long long)cap, thresh, edges, &ctl->edges);
+  k_poly_edges<<<hb, kPolyThreads, 0, st>>>(w.sorted, w.pairs, &w.ctl->pairs, (unsigned long long)cap, thresh, w.edges, &w.ctl->edges);
   S2A_LAUNCH_CHECK();
-  rc = launch_nms_edge_rounds(edges, (unsigned long long)cap, &ctl->edges, alive, (unsigned long long)cap, n, order, keep_orig,
-                              rounds_ws, rounds_bytes, st);
+  rc = launch_nms_edge_rounds(w.edges, (unsigned long long)cap, &w.ctl->edges, w.alive, (unsigned long long)cap, n, w.order, w.keep_orig,
+                              w.rounds_ws, w.rounds_bytes, st);
   if (rc != S2A_OK) return rc;
-  k_scene_count<<<nb, 256, 0, st>>>(keep_orig, order, seg_start, num_classes, cnt);
-  k_scene_write<<<nb, 256, 0, st>>>(keep_orig, order, key_s, seg_start, num_classes, cnt, nb, n, sorted, dets, ctl,
+  k_scene_count<<<nb, 256, 0, st>>>(w.keep_orig, w.order, w.seg_start, num_classes, w.cnt);
+  k_scene_write<<<nb, 256, 0, st>>>(w.keep_orig, w.order, w.key_s, w.seg_start, num_classes, w.cnt, nb, n, w.sorted, dets, w.ctl,
                                     (unsigned long long)cap, out_polys, out_scores, reinterpret_cast<long long*>(out_labels),
                                     reinterpret_cast<long long*>(out_src), reinterpret_cast<long long*>(class_counts),
                                     reinterpret_cast<long long*>(status));
