@@ -551,6 +551,39 @@ int s2a_conv_backward_weight_f16(const void* x, const void* g, void* grad_weight
                                  int64_t channels, int64_t height, int64_t width, int64_t out_channels, int ksize,
                                  void* workspace, size_t workspace_bytes, s2a_stream_t stream);
 
+/* The same for the stride-2 layers (FusedConv2d with own_grad_strided): ksize 3 / pad 1 / stride 2 with O % 128 == 0 (the
+ * forward's limit) or ksize 1 / pad 0 / stride 2; C and O multiples of 64; x [B,H,W,C], g [B,Ho,Wo,O] f16 with
+ * Ho = (H-1)/2+1, Wo = (W-1)/2+1; every tensor under 2^31 bytes and 16-byte aligned.  The forward is s2a_conv_nhwc_f16 with
+ * stride = 2, the filter pack and the prep pass (on [B*Ho*Wo, O]) are the ones above.  No workspace: every buffer these
+ * entry points write is an argument with a stated size.  No host read, no float atomic, no memset node, a fixed summation
+ * order: capturable and bit-identical from call to call.  Every check below is made before the first HIP call and
+ * answers S2A_EINVAL with a message.
+ * s2a_conv_backward_input_s2_f16: writes grad_input, f16 [B,H,W,C], all B*H*W*C elements and nothing else, from g and
+ *   packed_dgrad (the input-gradient filter of s2a_conv_pack_weight_train, O*C*k*k halfs).  ksize 3: input pixel
+ *   (2i+py, 2j+px) sums the taps of its parity class -- (0,0): w[1,1] g[i,j]; (0,1): w[1,0] g[i,j+1] + w[1,2] g[i,j];
+ *   (1,0): w[0,1] g[i+1,j] + w[2,1] g[i,j]; (1,1): w[0,0] g[i+1,j+1] + w[0,2] g[i+1,j] + w[2,0] g[i,j+1] + w[2,2] g[i,j] --
+ *   in this order over f32; a neighbour outside the map is neither loaded nor multiplied.  ksize 1:
+ *   grad_input[b,2i,2j,:] = W^T g[b,i,j,:], every pixel with an odd row or column is +0.
+ * s2a_conv_backward_weight_s2_slices: the number of position slices of the weight gradient, from the shapes only (the
+ *   same answer for the same shapes); 0 for a problem the entry point refuses (and for batch 0).
+ * s2a_conv_backward_weight_s2_f16: writes partial, f32 [slices][O][C*k*k], all slices*O*C*k*k elements and nothing else;
+ *   partial[s] is in the gradient's own layout [O,C,k,k] and holds the exact f32 sums, in tile order, over the position
+ *   tiles s, s + slices, ... (3x3: 4 x 16 output positions of one image; 1x1: 64 consecutive output positions) of
+ *   g[b,oy,ox,o] * x[b,2oy+ky-pad,2ox+kx-pad,c]; a slice without a tile holds exact zeros.  slices must be the query's
+ *   answer; anything else is refused with no buffer touched.
+ * s2a_conv_backward_weight_s2_reduce: out[e] = partial[0][e] + partial[1][e] + ... + partial[slices-1][e] in this order
+ *   over f32, e < count; out is count elements of out_dtype (F32, or F16 with one rounding). */
+int s2a_conv_backward_input_s2_f16(const void* g, const void* packed_dgrad, void* grad_input, int64_t batch,
+                                   int64_t channels, int64_t height, int64_t width, int64_t out_channels, int ksize,
+                                   s2a_stream_t stream);
+int s2a_conv_backward_weight_s2_slices(int64_t batch, int64_t channels, int64_t height, int64_t width,
+                                       int64_t out_channels, int ksize);
+int s2a_conv_backward_weight_s2_f16(const void* x, const void* g, void* partial, int slices, int64_t batch,
+                                    int64_t channels, int64_t height, int64_t width, int64_t out_channels, int ksize,
+                                    s2a_stream_t stream);
+int s2a_conv_backward_weight_s2_reduce(const void* partial, int slices, int64_t count, void* out, int out_dtype,
+                                       s2a_stream_t stream);
+
 /* Training side of the deformable convolution: the three device functions the reference's
  * backward is composed of (models/dcn/src/deform_conv_cuda_kernel.cu): deformable_im2col (:244-276),
  * deformable_col2im (:332-370), deformable_col2im_coord (:431-464).  p->batch = the number of images of

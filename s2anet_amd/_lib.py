@@ -161,6 +161,10 @@ SYMBOLS = {
     "s2a_conv_backward_weight_f16_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64, c_i64, c_i64, c_int]),
     "s2a_conv_backward_weight_f16": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_vp, c_sz,
                                              c_vp]),
+    "s2a_conv_backward_input_s2_f16": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_vp]),
+    "s2a_conv_backward_weight_s2_slices": (c_int, [c_i64, c_i64, c_i64, c_i64, c_i64, c_int]),
+    "s2a_conv_backward_weight_s2_f16": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_vp]),
+    "s2a_conv_backward_weight_s2_reduce": (c_int, [c_vp, c_int, c_i64, c_vp, c_int, c_vp]),
     "s2a_debug_read_stamps": (c_int, [c_vp, c_i64]),
     "s2a_build_flags": (c_int, []),
     "s2a_deform_conv_backward_input_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64, c_i64, c_i64]),

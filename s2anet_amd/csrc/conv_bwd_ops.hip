@@ -1,7 +1,8 @@
 // Training side of the regular convolutions (FusedConv2d with own_grad): the per-step filter pack, the backward's
 // preparation pass (ReLU mask + bias gradient) and the weight gradient.  The input gradient needs no kernel of its own: for a
 // stride-1 3x3 / pad-1 or 1x1 convolution it is s2a_conv_nhwc_f16 on the transposed, 180-degree-rotated filter, which the pack
-// below writes next to the forward filter.
+// below writes next to the forward filter.  The stride-2 layers (own_grad_strided) do need one -- k_conv_s2_bwd_input, from
+// the same packed filter -- and take the weight gradient kernel at ST = 2.
 #include <algorithm>
 
 #include "common.hpp"
@@ -119,12 +120,22 @@ __global__ void k_conv_bwd_bias_final(const float* __restrict__ partial, int nbl
 //   * k_conv_bwd_weight_reduce sums the slices' blocks in slice order (a slice without a tile wrote exact zeros).
 // EXEC: the transposing read needs all 64 lanes; a wave whose 32 out channels lie past the group takes no part AS A WHOLE
 // (mwave), and nothing inside the matrix section depends on the lane.
+// ST = 2 (the strided layers: 3x3 / s2 / p1 and 1x1 / s2): positions are those of the OUTPUT map [Ho, Wo], g is [B,Ho,Wo,O] and
+// x stays [B,H,W,C]; tap (ky, kx) of position (oy, ox) samples x[2 oy + ky - 1][2 ox + kx - 1] (1x1: x[2 oy][2 ox]).
+//   * a tap's 16 positions of a tile row are two pixels apart: read straight, rows 0/2 and 1/3 of a transposing read would
+//     start on the same banks.  A patch row is therefore staged as TWO images, 33 pixels in all: pixels 0..15 the even columns
+//     2 (tx0 + q), pixels 16..32 the odd columns 2 (tx0 + q) - 1, q = 0..16; kx = 1 reads the even image at q = p, kx = 0 the
+//     odd one at q = p and kx = 2 the odd one at q = p + 1 -- consecutive pixels again, the stride-1 read pattern;
+//   * the four patch rows are the input rows 2 (ty0 + r) + ky - 1;
+//   * a block of `partial` is the gradient's own layout: partial[slice][o][c][ky][kx] (s2a_conv_backward_weight_s2_f16).
 constexpr int kTPos = 64;                       // positions per tile
 constexpr int kOGroup = 256;                    // out channels per workgroup
 constexpr int kGoPitch = 576;                   // bytes per position of the g tile: 256 halfs + 64 (144 dwords = 16 mod 64: the four
                                                 // rows of a transposing read start in four different 16-bank groups)
 constexpr int kPatPitch = 192;                  // bytes per patch pixel: 64 halfs + 64 (48 dwords: rows start in banks 0, 48, 32, 16)
 constexpr int kPatW = 18;                       // 16 + 2 halo columns
+constexpr int kPatW2 = 33;                      // stride 2: 16 even + 17 odd columns
+constexpr int kS2MaxSlices = 32;                // stride 2: a slice is a whole [O][C k k] f32 image, the reduce reads them all
 constexpr int kWgradBlocks3 = 256, kWgradBlocks1 = 512;    // workgroups a launch aims at (3x3 / 1x1)
 
 struct WgradGeom {
@@ -144,13 +155,14 @@ inline WgradGeom wgrad_geom(int64_t B, int64_t C, int64_t H, int64_t W, int64_t 
   return q;
 }
 
-template <int KS>
+template <int KS, int ST = 1>
 __global__ __launch_bounds__(512, 2) void k_conv_bwd_weight(const _Float16* __restrict__ x,      // NHWC [B,H,W,C]
-                                                           const _Float16* __restrict__ g,      // NHWC [B,H,W,O]
+                                                           const _Float16* __restrict__ g,      // NHWC [B,Ho,Wo,O]
                                                            float* __restrict__ partial,         // [slice][owner][ostride][KS][64]
                                                            int B, int C, int H, int W, int O, int ksplit, int ostride,
-                                                           int ntiles) {
-  constexpr int kPatPix = KS == 3 ? 4 * kPatW : kTPos;
+                                                           int ntiles) {                        // (ST = 2: [slice][O][C][KS][KS])
+  constexpr int kPatRow = ST == 2 ? kPatW2 : kPatW;
+  constexpr int kPatPix = KS == 3 ? 4 * kPatRow : kTPos;
   constexpr int kPaVec = (kPatPix * 8 + 511) / 512;
   __shared__ __attribute__((aligned(16))) char s_go[kTPos * kGoPitch];
   __shared__ __attribute__((aligned(16))) char s_patch[kPatPix * kPatPitch];
@@ -160,8 +172,9 @@ __global__ __launch_bounds__(512, 2) void k_conv_bwd_weight(const _Float16* __re
   const int ky = owner % KS, cc = (owner / KS) % CC, og = owner / (KS * CC);
   const int o0 = og * kOGroup, Og = min(kOGroup, O - o0);
   const bool mwave = wave * 32 < Og;            // (Og is a multiple of 64: the wave's 32 out channels exist, or none does)
-  const int64_t HW = (int64_t)H * W, P = (int64_t)B * HW;
-  const int txn = (W + 15) / 16, tyn = (H + 3) / 4;
+  const int Ho = ST == 2 ? (H - 1) / 2 + 1 : H, Wo = ST == 2 ? (W - 1) / 2 + 1 : W;      // the map the positions live on
+  const int64_t HW = (int64_t)Ho * Wo, P = (int64_t)B * HW, HWx = (int64_t)H * W;
+  const int txn = (Wo + 15) / 16, tyn = (Ho + 3) / 4;
 
   f32x16b acc[KS][2];
 #pragma unroll
@@ -186,7 +199,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_bwd_weight(const _Float16* __re
       if (ch < Og) {
         if (KS == 3) {
           const int y = ty0 + (pos >> 4), xq = tx0 + (pos & 15);
-          if (y < H && xq < W) gv[i] = *reinterpret_cast<const f16x8b*>(g + ((int64_t)b * HW + (int64_t)y * W + xq) * O + o0 + ch);
+          if (y < Ho && xq < Wo) gv[i] = *reinterpret_cast<const f16x8b*>(g + ((int64_t)b * HW + (int64_t)y * Wo + xq) * O + o0 + ch);
         } else {
           const int64_t n = (int64_t)tile * kTPos + pos;
           if (n < P) gv[i] = *reinterpret_cast<const f16x8b*>(g + n * O + o0 + ch);
@@ -199,12 +212,22 @@ __global__ __launch_bounds__(512, 2) void k_conv_bwd_weight(const _Float16* __re
       pvv[i] = f16x8b{};
       if (v < kPatPix * 8) {
         if (KS == 3) {
-          const int yy = ty0 + pix / kPatW + ky - 1, xx = tx0 + pix % kPatW - 1;
+          const int pr = pix / kPatRow, pc = pix % kPatRow;
+          const int yy = ST == 2 ? 2 * (ty0 + pr) + ky - 1 : ty0 + pr + ky - 1;
+          const int xx = ST == 2 ? (pc < 16 ? 2 * (tx0 + pc) : 2 * (tx0 + pc - 16) - 1) : tx0 + pc - 1;
           if (yy >= 0 && yy < H && xx >= 0 && xx < W)
-            pvv[i] = *reinterpret_cast<const f16x8b*>(x + ((int64_t)b * HW + (int64_t)yy * W + xx) * C + cc * 64 + q);
+            pvv[i] = *reinterpret_cast<const f16x8b*>(x + ((int64_t)b * HWx + (int64_t)yy * W + xx) * C + cc * 64 + q);
         } else {
           const int64_t n = (int64_t)tile * kTPos + pix;
-          if (n < P) pvv[i] = *reinterpret_cast<const f16x8b*>(x + n * C + cc * 64 + q);
+          if (n < P) {
+            int64_t at = n;
+            if (ST == 2) {
+              const int64_t bi = n / HW;
+              const int rr = (int)(n - bi * HW);
+              at = bi * HWx + (int64_t)(2 * (rr / Wo)) * W + 2 * (rr % Wo);
+            }
+            pvv[i] = *reinterpret_cast<const f16x8b*>(x + at * C + cc * 64 + q);
+          }
         }
       }
     }
@@ -240,8 +263,8 @@ __global__ __launch_bounds__(512, 2) void k_conv_bwd_weight(const _Float16* __re
     int rows_in = 4, cols_in = 16;
     if (KS == 3) {
       const int r = tile % (tyn * txn);
-      rows_in = min(4, H - (r / txn) * 4);
-      cols_in = min(16, W - (r % txn) * 16);
+      rows_in = min(4, Ho - (r / txn) * 4);
+      cols_in = min(16, Wo - (r % txn) * 16);
     }
     if (mwave) {
       const int gq = lane >> 4, qq = (lane >> 2) & 3, pp = lane & 3;
@@ -267,7 +290,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_bwd_weight(const _Float16* __re
         for (int tl = 0; tl < KS; tl++)
 #pragma unroll
           for (int ct = 0; ct < 2; ct++) {
-            const int pix0 = KS == 3 ? ks * kPatW + tl : ks * 16;
+            const int pix0 = KS != 3 ? ks * 16 : ST == 2 ? ks * kPatW2 + (tl == 1 ? 0 : 16 + (tl >> 1)) : ks * kPatW + tl;
             f16x8b Bf = frag(b_base + pix0 * kPatPitch + ct * 64, kPatPitch);
             if (KS == 3 && cols_in < 16) Bf = __builtin_bit_cast(f16x8b, __builtin_bit_cast(s16x8b, Bf) & keep);
             acc[tl][ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, Bf, acc[tl][ct], 0, 0, 0);
@@ -277,7 +300,8 @@ __global__ __launch_bounds__(512, 2) void k_conv_bwd_weight(const _Float16* __re
   }
   // results: rows = out channels (4 consecutive per register quad), columns = channels of the chunk
   if (mwave) {
-    float* part = partial + (int64_t)blockIdx.x * ostride * (KS * 64);      // (blockIdx = slice * nowner + owner)
+    float* part = ST == 2 ? partial + (int64_t)slice * O * C * (KS * KS)
+                          : partial + (int64_t)blockIdx.x * ostride * (KS * 64);      // (blockIdx = slice * nowner + owner)
 #pragma unroll
     for (int tl = 0; tl < KS; tl++)
 #pragma unroll
@@ -285,7 +309,10 @@ __global__ __launch_bounds__(512, 2) void k_conv_bwd_weight(const _Float16* __re
 #pragma unroll
         for (int r = 0; r < 16; r++) {
           const int o = wave * 32 + 8 * (r >> 2) + (r & 3) + 4 * (lane >> 5);
-          part[(o * KS + tl) * 64 + ct * 32 + (lane & 31)] = acc[tl][ct][r];
+          if (ST == 2)
+            part[((int64_t)(o0 + o) * C + cc * 64 + ct * 32 + (lane & 31)) * (KS * KS) + ky * KS + tl] = acc[tl][ct][r];
+          else
+            part[(o * KS + tl) * 64 + ct * 32 + (lane & 31)] = acc[tl][ct][r];
         }
   }
 }
@@ -309,6 +336,153 @@ __global__ void k_conv_bwd_weight_reduce(const float* __restrict__ partial, int 
   float a = 0.f;
   for (int s = 0; s < ksplit; s++) a += p[s * step];
   gw[(((int64_t)o * C + cc * 64 + c) * KS + ky) * KS + kx] = (T)a;
+}
+
+// stride 2: out[e] = partial[0][e] + partial[1][e] + ... in slice order, f32 or (one rounding) f16
+template <typename T>
+__global__ void k_conv_bwd_weight_s2_reduce(const float* __restrict__ partial, int slices, int64_t count, T* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= count) return;
+  float a = 0.f;
+  for (int s = 0; s < slices; s++) a += partial[s * count + e];
+  out[e] = (T)a;
+}
+
+// ================================================================= input gradient, stride 2
+// A stride-2 convolution's input gradient is no stride-1 convolution of g.  Input pixel (y, x) = (2 i + py, 2 j + px) of the
+// 3x3 / p1 form receives, by parity class (g outside [0,Ho) x [0,Wo) takes no part),
+//   (0,0)  w[1,1] g[i,j]
+//   (0,1)  w[1,0] g[i,j+1] + w[1,2] g[i,j]
+//   (1,0)  w[0,1] g[i+1,j] + w[2,1] g[i,j]
+//   (1,1)  w[0,0] g[i+1,j+1] + w[0,2] g[i+1,j] + w[2,0] g[i,j+1] + w[2,2] g[i,j]
+// each w[ky,kx] g being the [C x O] . [O] product over the out channels: nine tap products per 2 x 2 input pixels, the
+// forward's count.  The 1x1 form is class (0,0) alone with its one tap; its other three pixels are written as +0.
+//   * a workgroup owns 4 x 16 quads (2 x 2 input pixels each) of one image and 64 input channels; wave (mt, half) holds
+//     channels 32 mt .. + 31 of the quads 32 half .. + 31, one 32 x 32 f32 accumulator per class;
+//   * per 64-out-channel chunk the g patch (5 x 17 pixels, 4 x 16 for 1x1; zeros outside the map, never loaded) is staged in LDS
+//     at a 144-byte pitch (36 dwords: the 16 pixels of a half-wave's 16-byte reads cover the 64 banks once); a lane's B
+//     fragment is 16 bytes of its quad's neighbour pixel;
+//   * the filter fragments come straight from s2a_conv_pack_weight_train's input-gradient filter (w'[c][o][8 - t], fragment
+//     order of frag_coords with the INPUT channels as rows): tap (ky, kx) of w is stage oc * taps + (taps - 1 - (3 ky + kx));
+//   * a quad whose neighbour row or column is outside the map keeps its accumulator instead of adding w . 0 (selected per
+//     lane behind the MFMA, in tiles on the bottom / right edge only; the branch is uniform).  Fixed order, no atomics.
+constexpr int kDgPitch = 144;
+
+template <int KS>
+__global__ __launch_bounds__(256) void k_conv_s2_bwd_input(const _Float16* __restrict__ g,        // NHWC [B,Ho,Wo,O]
+                                                           const _Float16* __restrict__ wpk,      // input-gradient filter
+                                                           _Float16* __restrict__ gx,             // NHWC [B,H,W,C]
+                                                           int C, int H, int W, int O) {
+  constexpr int HALO = KS == 3 ? 1 : 0, PC = 16 + HALO, NPIX = (4 + HALO) * PC, NVEC = (NPIX * 8 + 255) / 256;
+  constexpr int NCLS = KS == 3 ? 4 : 1, TAPS = KS * KS;
+  __shared__ __attribute__((aligned(16))) char s_g[NPIX * kDgPitch];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, mt = wave & 1, half = wave >> 1;
+  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, txn = (Wo + 15) / 16, tyn = (Ho + 3) / 4;
+  const int rt = blockIdx.x % (tyn * txn), b = blockIdx.x / (tyn * txn);
+  const int i0 = (rt / txn) * 4, j0 = (rt % txn) * 16, cg = blockIdx.y, G = C / 64;
+  const int n = half * 32 + (lane & 31), ti = n >> 4, tj = n & 15;      // the lane's quad of the tile
+  const int qi = i0 + ti, qj = j0 + tj;
+  const bool vi = qi + 1 < Ho, vj = qj + 1 < Wo;                        // the quad's lower / right neighbour exists
+  const bool edge = i0 + 4 >= Ho || j0 + 16 >= Wo;                      // (uniform) some quad of the tile lacks one
+
+  f32x16b acc[NCLS];
+#pragma unroll
+  for (int a = 0; a < NCLS; a++)
+#pragma unroll
+    for (int r = 0; r < 16; r++) acc[a][r] = 0.f;
+
+  auto mac = [&](f32x16b& d, const f16x8b& A, const f16x8b& Bf, bool ok) {
+    const f32x16b t = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, Bf, d, 0, 0, 0);
+    if (KS == 3 && edge) {
+#pragma unroll
+      for (int r = 0; r < 16; r++) d[r] = ok ? t[r] : d[r];
+    } else {
+      d = t;
+    }
+  };
+
+  // a thread's vectors of the g patch are requested one chunk ahead, the filter fragments of a k-step (16 out channels, TAPS x
+  // 16 bytes a lane) one step ahead: both are in flight under the MFMAs
+  f16x8b gv[NVEC];
+  auto issue = [&](int oc) {
+#pragma unroll
+    for (int i = 0; i < NVEC; i++) {
+      const int v = tid + 256 * i, pix = v >> 3, q = (v & 7) * 8, y = i0 + pix / PC, xq = j0 + pix % PC;
+      gv[i] = f16x8b{};
+      if (v < NPIX * 8 && y < Ho && xq < Wo)
+        gv[i] = *reinterpret_cast<const f16x8b*>(g + (((int64_t)b * Ho + y) * Wo + xq) * O + oc * 64 + q);
+    }
+  };
+  auto land = [&]() {                            // (zeros included: every byte the matrix section reads is rewritten per chunk)
+#pragma unroll
+    for (int i = 0; i < NVEC; i++) {
+      const int v = tid + 256 * i;
+      if (v < NPIX * 8) *reinterpret_cast<f16x8b*>(s_g + (v >> 3) * kDgPitch + (v & 7) * 16) = gv[i];
+    }
+  };
+  // fragment (stage = oc TAPS + t, cg, mt, kk) of the pack: 64 lanes x 8 halfs; tap (ky, kx) of w is t = TAPS - 1 - (ky KS + kx)
+  const _Float16* wbase = wpk + ((int64_t)cg * 2 + mt) * 4 * 512 + lane * 8;
+  const int steps = O / 16;
+  f16x8b wa[TAPS], wn[TAPS];
+  auto wload = [&](f16x8b(&dst)[TAPS], int step) {
+#pragma unroll
+    for (int t = 0; t < TAPS; t++)
+      dst[t] = *reinterpret_cast<const f16x8b*>(wbase + ((int64_t)((step >> 2) * TAPS + t) * G * 8 + (step & 3)) * 512);
+  };
+  auto tap = [&](int ky, int kx) -> const f16x8b& { return wa[TAPS - 1 - (ky * KS + kx)]; };
+
+  issue(0);
+  wload(wa, 0);
+  for (int oc = 0; oc < O / 64; oc++) {
+    __syncthreads();                             // the previous chunk's patch has been read
+    land();
+    __syncthreads();
+    if (oc + 1 < O / 64) issue(oc + 1);
+#pragma unroll
+    for (int kk = 0; kk < 4; kk++) {
+      wload(wn, min(oc * 4 + kk + 1, steps - 1));           // (the last step asks for itself again: in bounds, not used)
+      const char* bp = s_g + (ti * PC + tj) * kDgPitch + kk * 32 + (lane >> 5) * 16;
+      const f16x8b g00 = *reinterpret_cast<const f16x8b*>(bp);
+      if (KS == 1) {
+        mac(acc[0], tap(0, 0), g00, true);
+      } else {
+        const f16x8b g01 = *reinterpret_cast<const f16x8b*>(bp + kDgPitch);
+        const f16x8b g10 = *reinterpret_cast<const f16x8b*>(bp + PC * kDgPitch);
+        const f16x8b g11 = *reinterpret_cast<const f16x8b*>(bp + (PC + 1) * kDgPitch);
+        mac(acc[0], tap(1, 1), g00, true);
+        mac(acc[1], tap(1, 0), g01, vj);
+        mac(acc[1], tap(1, 2), g00, true);
+        mac(acc[2], tap(0, 1), g10, vi);
+        mac(acc[2], tap(2, 1), g00, true);
+        mac(acc[3], tap(0, 0), g11, vi && vj);
+        mac(acc[3], tap(0, 2), g10, vi);
+        mac(acc[3], tap(2, 0), g01, vj);
+        mac(acc[3], tap(2, 2), g00, true);
+      }
+#pragma unroll
+      for (int t = 0; t < TAPS; t++) wa[t] = wn[t];
+    }
+  }
+  // results: column (lane & 31) = the lane's quad, register quad rq = channels 8 rq + 4 (lane >> 5) .. + 3 of the wave's 32
+  if (qi < Ho && qj < Wo) {
+#pragma unroll
+    for (int cls = 0; cls < 4; cls++) {
+      const int y = 2 * qi + (cls >> 1), xq = 2 * qj + (cls & 1);
+      if (y < H && xq < W) {
+        _Float16* dst = gx + (((int64_t)b * H + y) * W + xq) * C + cg * 64 + mt * 32 + 4 * (lane >> 5);
+#pragma unroll
+        for (int rq = 0; rq < 4; rq++) {
+          using f16x4b = __attribute__((ext_vector_type(4))) _Float16;
+          f16x4b o = f16x4b{};                   // (1x1: the three other pixels of the quad are +0)
+          if (cls < NCLS) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) o[j] = (_Float16)acc[cls < NCLS ? cls : 0][4 * rq + j];
+          }
+          *reinterpret_cast<f16x4b*>(dst + 8 * rq) = o;
+        }
+      }
+    }
+  }
 }
 
 inline bool dtype_ok(int d) { return d == S2A_DTYPE_F32 || d == S2A_DTYPE_F16; }
@@ -443,6 +617,96 @@ extern "C" int s2a_conv_backward_weight_f16(const void* x, const void* g, void* 
     else
       k_conv_bwd_weight_reduce<1, _Float16><<<rb, 256, 0, st>>>(partial, C, O, q.ksplit, q.ostride, (_Float16*)grad_weight);
   }
+  S2A_LAUNCH_CHECK();
+  return S2A_OK;
+}
+
+// ================================================================= stride 2 (3x3 / p1 and 1x1): input and weight gradient
+namespace {
+// what is wrong with a strided problem, or nullptr: the checks the entry points and the slices query share
+const char* s2_shape_problem(int64_t B, int64_t C, int64_t H, int64_t W, int64_t O, int ksize) {
+  if (ksize != 3 && ksize != 1) return "kernel size must be 1 or 3";
+  if (!(B >= 0 && C > 0 && O > 0 && H > 0 && W > 0)) return "bad shape";
+  if (C % 64 != 0 || O % 64 != 0) return "channel counts must be multiples of 64";
+  if (ksize == 3 && O % 128 != 0) return "3x3 stride 2 needs out_channels % 128 == 0";
+  const uint64_t Ho = (uint64_t)(H - 1) / 2 + 1, Wo = (uint64_t)(W - 1) / 2 + 1;
+  if (!(H < 32000 && W < 32000 && B < (1ll << 31) && C < (1ll << 24) && O < (1ll << 24) &&
+        (uint64_t)B * H * W * C * 2 < (1ull << 31) && (uint64_t)B * Ho * Wo * O * 2 < (1ull << 31) &&
+        (uint64_t)O * C * ksize * ksize * 4 < (1ull << 31)))
+    return "tensor too large for 32-bit offsets (2^31 bytes or more)";
+  return nullptr;
+}
+}  // namespace
+
+extern "C" int s2a_conv_backward_input_s2_f16(const void* g, const void* packed_dgrad, void* grad_input, int64_t batch,
+                                              int64_t channels, int64_t height, int64_t width, int64_t out_channels,
+                                              int ksize, s2a_stream_t stream) {
+  const char* problem = s2_shape_problem(batch, channels, height, width, out_channels, ksize);
+  S2A_CHECK_ARG(!problem, "conv_backward_input_s2: %s", problem);
+  if (batch == 0) return S2A_OK;
+  S2A_CHECK_ARG(g && packed_dgrad && grad_input, "conv_backward_input_s2: NULL tensor");
+  S2A_CHECK_ARG(aligned16(g) && aligned16(packed_dgrad) && aligned16(grad_input),
+                "conv_backward_input_s2: tensors must be 16-byte aligned");
+  const int64_t Ho = (height - 1) / 2 + 1, Wo = (width - 1) / 2 + 1;
+  const int64_t tiles = batch * ((Ho + 3) / 4) * ((Wo + 15) / 16);
+  S2A_CHECK_ARG(tiles < (1ll << 31) && channels / 64 < 65536, "conv_backward_input_s2: too many tiles");
+  const dim3 grid((unsigned)tiles, (unsigned)(channels / 64));
+  hipStream_t st = as_stream(stream);
+  const int C = (int)channels, H = (int)height, W = (int)width, O = (int)out_channels;
+  if (ksize == 3)
+    k_conv_s2_bwd_input<3><<<grid, 256, 0, st>>>((const _Float16*)g, (const _Float16*)packed_dgrad, (_Float16*)grad_input, C, H, W, O);
+  else
+    k_conv_s2_bwd_input<1><<<grid, 256, 0, st>>>((const _Float16*)g, (const _Float16*)packed_dgrad, (_Float16*)grad_input, C, H, W, O);
+  S2A_LAUNCH_CHECK();
+  return S2A_OK;
+}
+
+extern "C" int s2a_conv_backward_weight_s2_slices(int64_t batch, int64_t channels, int64_t height, int64_t width,
+                                                  int64_t out_channels, int ksize) {
+  if (s2_shape_problem(batch, channels, height, width, out_channels, ksize) || batch == 0) return 0;
+  const WgradGeom q = wgrad_geom(batch, channels, (height - 1) / 2 + 1, (width - 1) / 2 + 1, out_channels, ksize);
+  return std::min(q.ksplit, kS2MaxSlices);      // (shapes only, as ksplit)
+}
+
+extern "C" int s2a_conv_backward_weight_s2_f16(const void* x, const void* g, void* partial, int slices, int64_t batch,
+                                               int64_t channels, int64_t height, int64_t width, int64_t out_channels,
+                                               int ksize, s2a_stream_t stream) {
+  const char* problem = s2_shape_problem(batch, channels, height, width, out_channels, ksize);
+  S2A_CHECK_ARG(!problem, "conv_backward_weight_s2: %s", problem);
+  S2A_CHECK_ARG(batch > 0, "conv_backward_weight_s2: bad shape (an empty batch has no slices)");
+  const int want = s2a_conv_backward_weight_s2_slices(batch, channels, height, width, out_channels, ksize);
+  S2A_CHECK_ARG(slices == want, "conv_backward_weight_s2: slices is %d, s2a_conv_backward_weight_s2_slices answers %d", slices, want);
+  S2A_CHECK_ARG(x && g && partial, "conv_backward_weight_s2: NULL tensor");
+  S2A_CHECK_ARG(aligned16(x) && aligned16(g) && aligned16(partial), "conv_backward_weight_s2: tensors must be 16-byte aligned");
+  const WgradGeom q = wgrad_geom(batch, channels, (height - 1) / 2 + 1, (width - 1) / 2 + 1, out_channels, ksize);
+  S2A_CHECK_ARG(q.ntiles < (1ll << 31), "conv_backward_weight_s2: too many tiles");
+  hipStream_t st = as_stream(stream);
+  const unsigned grid = (unsigned)(slices * q.nowner);
+  const int B = (int)batch, C = (int)channels, H = (int)height, W = (int)width, O = (int)out_channels;
+  if (ksize == 3)
+    k_conv_bwd_weight<3, 2><<<grid, 512, 0, st>>>((const _Float16*)x, (const _Float16*)g, (float*)partial, B, C, H, W, O, slices,
+                                                  q.ostride, (int)q.ntiles);
+  else
+    k_conv_bwd_weight<1, 2><<<grid, 512, 0, st>>>((const _Float16*)x, (const _Float16*)g, (float*)partial, B, C, H, W, O, slices,
+                                                  q.ostride, (int)q.ntiles);
+  S2A_LAUNCH_CHECK();
+  return S2A_OK;
+}
+
+extern "C" int s2a_conv_backward_weight_s2_reduce(const void* partial, int slices, int64_t count, void* out, int out_dtype,
+                                                  s2a_stream_t stream) {
+  S2A_CHECK_ARG(slices > 0 && count >= 0, "conv_backward_weight_s2_reduce: bad shape");
+  S2A_CHECK_ARG((uint64_t)count * 4 < (1ull << 31), "conv_backward_weight_s2_reduce: tensor too large for 32-bit offsets");
+  S2A_CHECK_ARG(dtype_ok(out_dtype), "conv_backward_weight_s2_reduce: output dtype must be f32 or f16");
+  if (count == 0) return S2A_OK;
+  S2A_CHECK_ARG(partial && out, "conv_backward_weight_s2_reduce: NULL tensor");
+  S2A_CHECK_ARG(aligned16(partial) && aligned16(out), "conv_backward_weight_s2_reduce: tensors must be 16-byte aligned");
+  hipStream_t st = as_stream(stream);
+  const unsigned rb = (unsigned)((count + 255) / 256);
+  if (out_dtype == S2A_DTYPE_F32)
+    k_conv_bwd_weight_s2_reduce<float><<<rb, 256, 0, st>>>((const float*)partial, slices, count, (float*)out);
+  else
+    k_conv_bwd_weight_s2_reduce<_Float16><<<rb, 256, 0, st>>>((const float*)partial, slices, count, (_Float16*)out);
   S2A_LAUNCH_CHECK();
   return S2A_OK;
 }

@@ -385,6 +385,31 @@ def _train_limits(x, w, b, kernel_size, stride, padding, dilation, groups, resid
     return B * H * W * C * 2 < (1 << 31) and B * H * W * O * 2 < (1 << 31)
 
 
+def train_conv_strided_ok(x, conv, residual=None):
+    """limits of the own training route of the stride-2 layers (FusedConvS2Function), and nothing but limits: stride (2, 2),
+    3x3 / pad 1 with O % 128 == 0 (the forward kernel's limit) or 1x1 / pad 0, dilation 1, groups 1, C and O multiples of 64,
+    f16 channels-last x on the GPU, f16 or f32 weight with a bias of the same dtype or none, a residual of the OUTPUT's
+    shape and layout, input and output under 2^31 bytes.  No speed heuristic plays a part, as in train_conv_ok."""
+    if not (x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 and x.numel() > 0 and
+            x.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    k, pd, C, O = tuple(conv.kernel_size), tuple(conv.padding), conv.in_channels, conv.out_channels
+    if not (tuple(conv.dilation) == (1, 1) and conv.groups == 1 and tuple(conv.stride) == (2, 2) and
+            ((k == (3, 3) and pd == (1, 1) and O % 128 == 0) or (k == (1, 1) and pd == (0, 0))) and
+            C % 64 == 0 and O % 64 == 0 and x.shape[1] == C):
+        return False
+    w, b = conv.weight, conv.bias
+    if w.dtype not in (torch.float16, torch.float32) or not w.is_cuda or (b is not None and b.dtype != w.dtype):
+        return False
+    B, _, H, W = x.shape
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    if residual is not None and not (residual.is_cuda and residual.dtype == torch.float16 and
+                                     tuple(residual.shape) == (B, O, Ho, Wo) and
+                                     residual.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    return B * H * W * C * 2 < (1 << 31) and B * Ho * Wo * O * 2 < (1 << 31) and O * C * k[0] * k[1] * 4 < (1 << 31)
+
+
 def train_pad_widths(x, conv):
     """deterministic mode only: (C', O') when the layer fails train_conv_ok for its width alone and passes at the zero-padded
     width -- fewer than 64 filters (the 5- and 15-map prediction convs: O' = 64) over C % 64 == 0 or C == 32 inputs, or 32
@@ -411,10 +436,13 @@ def padded_train_conv(x, weight, bias, relu, Cp, Op):
     return out if Op == O else out[:, :O]
 
 
-def train_kernels(module, enabled=True):
+def train_kernels(module, enabled=True, strided=False):
     """own_grad = enabled on every FusedConv2d of the tree -> how many were set.  With own_grad a grad-enabled forward of
     an eligible layer (train_conv_ok) runs FusedConvFunction: forward, input gradient, weight gradient, bias gradient and
     ReLU mask on the project's kernels.  Every other layer and every other call keeps its route.
+    strided=True: a second opt-in, own_grad_strided = enabled on the same modules (not set or cleared otherwise) -- the
+    stride-2 layers (train_conv_strided_ok: the 3x3 / s2 conv2 and the 1x1 / s2 downsample of a stage's first bottleneck,
+    FPN's two extra levels) run FusedConvS2Function under grad.  The return value is the same count.
     In deterministic mode (s2anet_amd.deterministic) own_grad also takes the layers that fail train_conv_ok for their width
     alone (train_pad_widths) and, set here as well but not counted, the ORConv2d modules of the tree."""
     from .orn import ORConv2d
@@ -422,10 +450,58 @@ def train_kernels(module, enabled=True):
     for m in module.modules():
         if isinstance(m, FusedConv2d):
             m.own_grad = bool(enabled)
+            if strided:
+                m.own_grad_strided = bool(enabled)
             n += 1
         elif isinstance(m, ORConv2d):
             m.own_grad = bool(enabled)
     return n
+
+
+def _train_forward(ctx, x, weight, bias, residual, relu, stride):
+    """the forward both training Functions share: pack (forward order and, when x wants a gradient, input-gradient order),
+    s2a_conv_nhwc_f16 at `stride` with bias and residual fused, the stock in-place ReLU; saves what the backward needs"""
+    O, C, k, _ = weight.shape
+    L = _lib.lib()
+    need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    w = weight.detach()
+    w = w if w.is_contiguous() else w.contiguous()            # (a channels-last 3x3 filter: one stock copy)
+    fwd = torch.empty((w.numel(),), dtype=torch.float16, device=x.device)
+    dgrad = torch.empty_like(fwd) if need_x else None
+    with torch.cuda.device(x.device):
+        _lib.check(L.s2a_conv_pack_weight_train(_lib.ptr(w), _lib.dtype_code(w), O, C, k, _lib.ptr(fwd), _lib.ptr(dgrad),
+                                                _lib.stream_ptr(x.device)))
+    # the launch's fused ReLU is inference's (NaN -> 0, include/s2anet_hip.h): training runs it with relu = 0 and
+    # applies the stock in-place ReLU, which keeps a NaN; the finite entries get the same bits either way
+    out = conv_f16(x, fwd, None if bias is None else bias.detach(), O, k, stride, False, residual)
+    if relu:
+        out.relu_()
+    ctx.save_for_backward(x if need_w else None, out if relu else None, dgrad)
+    ctx.geom = (tuple(x.shape), O, k, weight.dtype, None if bias is None else bias.dtype)
+    return out
+
+
+def _train_prep(ctx, grad_out, out, positions):
+    """the backward's first pass (s2a_conv_backward_prep_f16 on [positions, O]) -> (g, grad_bias): g = grad_out behind the ReLU
+    mask as dense f16 channels-last (grad_out itself without a ReLU, or when nothing needs it), the bias gradient or None"""
+    O, bdtype = ctx.geom[1], ctx.geom[4]
+    need_x, need_w, need_b, need_r = ctx.needs_input_grad[:4]
+    L, dev = _lib.lib(), grad_out.device
+    go = grad_out if grad_out.dtype == torch.float16 else grad_out.to(torch.float16)
+    go = go.contiguous(memory_format=torch.channels_last)
+    g, gb = go, None
+    need_g = need_x or need_w or need_r
+    if (out is not None and need_g) or need_b:
+        if out is not None and need_g:
+            g = torch.empty_like(go)
+        ws = None
+        if need_b:
+            gb = torch.empty((O,), dtype=bdtype, device=dev)
+            ws = torch.empty((L.s2a_conv_backward_prep_f16_workspace_bytes(positions, O),), dtype=torch.uint8, device=dev)
+        _lib.check(L.s2a_conv_backward_prep_f16(_lib.ptr(go), _lib.ptr(out), _lib.ptr(g if g is not go else None),
+                                                _lib.ptr(gb), 0 if gb is None else _lib.dtype_code(gb), positions, O,
+                                                _lib.ptr(ws), 0 if ws is None else ws.numel(), _lib.stream_ptr(dev)))
+    return g, gb
 
 
 class FusedConvFunction(torch.autograd.Function):
@@ -439,61 +515,69 @@ class FusedConvFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, residual, relu):
-        O, C, k, _ = weight.shape
-        L = _lib.lib()
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        w = weight.detach()
-        w = w if w.is_contiguous() else w.contiguous()            # (a channels-last 3x3 filter: one stock copy)
-        fwd = torch.empty((w.numel(),), dtype=torch.float16, device=x.device)
-        dgrad = torch.empty_like(fwd) if need_x else None
-        with torch.cuda.device(x.device):
-            _lib.check(L.s2a_conv_pack_weight_train(_lib.ptr(w), _lib.dtype_code(w), O, C, k, _lib.ptr(fwd), _lib.ptr(dgrad),
-                                                    _lib.stream_ptr(x.device)))
-        # the launch's fused ReLU is inference's (NaN -> 0, include/s2anet_hip.h): training runs it with relu = 0 and
-        # applies the stock in-place ReLU, which keeps a NaN; the finite entries get the same bits either way
-        out = conv_f16(x, fwd, None if bias is None else bias.detach(), O, k, 1, False, residual)
-        if relu:
-            out.relu_()
-        ctx.save_for_backward(x if need_w else None, out if relu else None, dgrad)
-        ctx.geom = (tuple(x.shape), O, k, weight.dtype, None if bias is None else bias.dtype)
-        return out
+        return _train_forward(ctx, x, weight, bias, residual, relu, 1)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         x, out, dgrad = ctx.saved_tensors
-        (B, C, H, W), O, k, wdtype, bdtype = ctx.geom
-        need_x, need_w, need_b, need_r = ctx.needs_input_grad[:4]
+        (B, C, H, W), O, k, wdtype, _ = ctx.geom
+        need_x, need_w, _, need_r = ctx.needs_input_grad[:4]
         L, dev = _lib.lib(), grad_out.device
-        go = grad_out if grad_out.dtype == torch.float16 else grad_out.to(torch.float16)
-        go = go.contiguous(memory_format=torch.channels_last)
-        st = _lib.stream_ptr(dev)
-        g, gb = go, None
-        need_g = need_x or need_w or need_r
         with torch.cuda.device(dev):
-            if (out is not None and need_g) or need_b:
-                if out is not None and need_g:
-                    g = torch.empty_like(go)
-                ws = None
-                if need_b:
-                    gb = torch.empty((O,), dtype=bdtype, device=dev)
-                    ws = torch.empty((L.s2a_conv_backward_prep_f16_workspace_bytes(B * H * W, O),), dtype=torch.uint8, device=dev)
-                _lib.check(L.s2a_conv_backward_prep_f16(_lib.ptr(go), _lib.ptr(out), _lib.ptr(g if g is not go else None),
-                                                        _lib.ptr(gb), 0 if gb is None else _lib.dtype_code(gb), B * H * W, O,
-                                                        _lib.ptr(ws), 0 if ws is None else ws.numel(), st))
+            g, gb = _train_prep(ctx, grad_out, out, B * H * W)
             gx = conv_f16(g, dgrad, None, C, k, 1, False) if need_x else None
             gw = None
             if need_w:
                 gw = torch.empty((O, C, k, k), dtype=wdtype, device=dev)
                 ws = torch.empty((L.s2a_conv_backward_weight_f16_workspace_bytes(B, C, H, W, O, k),), dtype=torch.uint8, device=dev)
                 _lib.check(L.s2a_conv_backward_weight_f16(_lib.ptr(x), _lib.ptr(g), _lib.ptr(gw), _lib.dtype_code(gw), B, C, H, W,
-                                                          O, k, _lib.ptr(ws), ws.numel(), st))
+                                                          O, k, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+        return gx, gw, gb, (g if need_r else None), None
+
+
+class FusedConvS2Function(torch.autograd.Function):
+    """FusedConvFunction for the stride-2 layers (train_conv_strided_ok): 3x3 / pad 1 or 1x1, stride 2.  Pack, forward (at
+    stride 2) and prep (on [B Ho Wo, O]) are shared with it; the backward then runs s2a_conv_backward_input_s2_f16 (a
+    stride-2 convolution's input gradient is no convolution of g: four parity classes of the input pixel, nine tap products
+    per 2 x 2 pixels) and s2a_conv_backward_weight_s2_f16 + _reduce (per-slice f32 sums in the gradient's layout, summed in
+    slice order).  Only what needs_input_grad asks for is computed.  No host read, no float atomic, no memset node, geometry
+    from shapes only, buffers from the torch allocator: capturable, and bit-equal from run to run."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, relu):
+        return _train_forward(ctx, x, weight, bias, residual, relu, 2)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, out, dgrad = ctx.saved_tensors
+        (B, C, H, W), O, k, wdtype, _ = ctx.geom
+        need_x, need_w, _, need_r = ctx.needs_input_grad[:4]
+        L, dev = _lib.lib(), grad_out.device
+        st = _lib.stream_ptr(dev)
+        gx = gw = None
+        with torch.cuda.device(dev):
+            g, gb = _train_prep(ctx, grad_out, out, B * ((H - 1) // 2 + 1) * ((W - 1) // 2 + 1))
+            if need_x:
+                gx = torch.empty((B, C, H, W), dtype=torch.float16, device=dev, memory_format=torch.channels_last)
+                _lib.check(L.s2a_conv_backward_input_s2_f16(_lib.ptr(g), _lib.ptr(dgrad), _lib.ptr(gx), B, C, H, W, O, k, st))
+            if need_w:
+                slices = L.s2a_conv_backward_weight_s2_slices(B, C, H, W, O, k)
+                partial = torch.empty((slices, O, C * k * k), dtype=torch.float32, device=dev)
+                gw = torch.empty((O, C, k, k), dtype=wdtype, device=dev)
+                _lib.check(L.s2a_conv_backward_weight_s2_f16(_lib.ptr(x), _lib.ptr(g), _lib.ptr(partial), slices, B, C, H, W, O,
+                                                             k, st))
+                _lib.check(L.s2a_conv_backward_weight_s2_reduce(_lib.ptr(partial), slices, gw.numel(), _lib.ptr(gw),
+                                                                _lib.dtype_code(gw), st))
         return gx, gw, gb, (g if need_r else None), None
 
 
 class FusedConv2d(nn.Conv2d):
     """nn.Conv2d + (bias, optional residual, optional ReLU) epilogue in one pass"""
     own_grad = False        # train_kernels(): grad-enabled forwards of eligible layers (train_conv_ok) run FusedConvFunction
+    own_grad_strided = False    # train_kernels(strided=True): those of the stride-2 layers (train_conv_strided_ok) run
+    #                             FusedConvS2Function
 
     def __init__(self, *args, relu=False, **kw):
         super().__init__(*args, **kw)
@@ -547,6 +631,9 @@ class FusedConv2d(nn.Conv2d):
         if out is None and self.own_grad and _needs_grad(x, self.weight, self.bias, residual) and \
                 train_conv_ok(x, self, residual):
             return FusedConvFunction.apply(x, self.weight, self.bias, residual, self.fuse_relu)   # (chain= is ignored, as under grad)
+        if out is None and self.own_grad_strided and _needs_grad(x, self.weight, self.bias, residual) and \
+                train_conv_strided_ok(x, self, residual):
+            return FusedConvS2Function.apply(x, self.weight, self.bias, residual, self.fuse_relu)
         if out is None and residual is None and self.own_grad and _lib.deterministic() and _needs_grad(x, self.weight, self.bias):
             pad = train_pad_widths(x, self)
             if pad is not None:     # deterministic mode: the library's weight gradient is not reproducible, the padded own route is
