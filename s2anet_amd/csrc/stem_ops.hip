@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "common.hpp"
 
@@ -23,18 +24,21 @@ namespace {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+using h2 = __attribute__((ext_vector_type(2))) _Float16;
 using h4 = __attribute__((ext_vector_type(4))) _Float16;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
+using i16x8 = __attribute__((ext_vector_type(8))) short;
 
 constexpr int kKSteps = 11;                 // 176 = 22 groups of 8 K entries; group q: ky = q / 3, g = q % 3
 constexpr int kInRows = 40;                 // 39 patch rows + one zero row for the padded K tail (ky = 7)
 constexpr int kInPitch = 136;               // halfs per patch row: 117 used, reads reach index 119
-constexpr int kInDw = 31;                   // aligned dwords per patch row (124 bytes from byte -1)
+constexpr int kInDw = 31;                   // aligned dwords per patch row (124 bytes from byte -1); a 32nd is carried along unused
 constexpr int kConvPitch = 144;             // bytes per staged conv pixel: 64 halfs + 16 B pad
 constexpr int kInBytes = kInRows * kInPitch * 2;                    // 10880
 constexpr int kConvBytes = 289 * kConvPitch;                        // 41616
 constexpr int kStemLds = 640 + 2 * kKSteps * 64 * 16 + (kInBytes > kConvBytes ? kInBytes : kConvBytes);   // table + bias + filter + patch / conv tile
-constexpr int kInIters = (kInRows * kInDw + 255) / 256;             // 5 dwords per thread
+constexpr int kInIters = kInRows / 8;                               // 5 dwords per thread: 8 rows of 32 dwords per pass of the workgroup
+static_assert(kInRows % 8 == 0 && 4 * kInDw + 2 < kInPitch, "patch passes");
 
 // filter [64][3][7][7] f16 -> [m 2][step 11][lane 64][8]: lane l, element j =
 // W[m*32 + (l & 31)][k = 16*step + 8*(l >> 5) + j], k = ky*24 + kx*3 + c (zero where kx*3+c > 20 or ky > 6)
@@ -57,7 +61,24 @@ __global__ void k_stem_pack(const _Float16* __restrict__ w, _Float16* __restrict
 // per workgroup (fetched per tile into every wave's registers they cost 90 KB per tile through the CU's load path and
 // 88 VGPRs), and the NEXT tile's patch dwords are requested right after the current patch has been converted, so their
 // round trip runs under the MFMA / epilogue / pooling phases of the current tile.
+//
+// Everything a tile does not need to redo is done once (66 MFMAs per wave and tile stood against 1.6 k vector-ALU
+// instructions before this layout; with those halved the LDS array is what binds, docs/HISTORY.md "Round 9"):
+//   * what depends on the thread alone (its patch items, its conv pixels, its pooled outputs, the f32 bias of its
+//     accumulator rows) is worked out before the tile loop, and a tile's (tx, ty, b) once, when its patch is requested;
+//   * `wave` is made provably uniform and every wave runs the same five accumulator units (below), so there is no
+//     "this wave has no third pixel tile" exec mask with the accumulators copied round it; the fragments of step
+//     s + 1 are read while step s multiplies;
+//   * the epilogue rounds a pair, takes the ReLU on the rounded halves (rounding is monotonic and keeps zero, so
+//     max(round(v), 0) == round(max(v, 0)); NaN -> 0 either way) and selects once per 8-byte store; the pooling is a
+//     packed max (the staged values are never NaN);
+//   * a patch dword outside the image becomes 0 before the table (entry 0 is +0), and its four halves leave as
+//     b16 + b32 + b16 (index 4d is 4-byte aligned; the patch starts 16 bytes into its buffer so that the half before
+//     a row may always be written).
+// None of this changes a value: MFMA, K layout, step order per accumulator, table and epilogue roundings are the same.
 constexpr int kWBytes = 2 * kKSteps * 64 * 16;                          // 22528
+constexpr int kInLead = 16;                                             // bytes in front of the patch (see above)
+static_assert(kInLead + kInBytes <= kConvBytes, "the patch lies inside the conv staging buffer");
 __global__ __launch_bounds__(256, 2) void k_stem(const uint8_t* __restrict__ img,      // [B,H,W,3]
                                                  const _Float16* __restrict__ wp,     // k_stem_pack
                                                  const _Float16* __restrict__ bias,   // [64] or null
@@ -68,115 +89,154 @@ __global__ __launch_bounds__(256, 2) void k_stem(const uint8_t* __restrict__ img
   _Float16* s_lut = reinterpret_cast<_Float16*>(smem);                 // 256 halfs
   _Float16* s_bias = reinterpret_cast<_Float16*>(smem + 512);          // 64 halfs
   const char* s_w = smem + 640;                                        // filter fragments [m 2][step 11][lane 64] x 16 B
-  _Float16* s_in = reinterpret_cast<_Float16*>(smem + 640 + kWBytes);
   char* s_conv = smem + 640 + kWBytes;                                 // aliases the patch (dead by then)
+  _Float16* s_in = reinterpret_cast<_Float16*>(s_conv + kInLead);
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int hsel = lane >> 5;
   const int64_t row_bytes = (int64_t)W * 3;
 
-  // patch dwords of tile t: unconditional loads from a clamped address, so none waits for the previous one
+  // ---- per thread, once: its patch dwords (rows pr0 + 8 it, aligned dword pd of the row) and its share of the GEMM.
+  // The 10 pixel tiles of 32 (320 >= 289 conv pixels) times the two halves of the 64 maps are 20 units of one 32x32
+  // accumulator; every wave takes five: both halves of pixel tiles w and w + 4, and half (w & 1) of pixel tile
+  // 8 + (w >> 1).  (Whole pixel tiles per wave made waves 0 and 1 run 66 MFMAs and the other two 44.)
+  const int pr0 = tid >> 5, pd = tid & 31;
+  const int m3 = wave & 1;
+  int ny[3], nx[3];
+  bool nok3;                                                   // pixel tile 9 holds pixel 288 alone
+  const _Float16 *pbase_n[3], *pbase_w[3];
+#pragma unroll
+  for (int p = 0; p < 3; p++) {
+    int n = (p < 2 ? wave + 4 * p : 8 + (wave >> 1)) * 32 + (lane & 31);
+    if (p == 2) nok3 = n < 289;
+    n = n < 289 ? n : 0;
+    ny[p] = n / 17;
+    nx[p] = n - 17 * ny[p];
+    const int pbase = (2 * ny[p]) * kInPitch + 6 * nx[p];     // half index of tap (0,0), channel 0
+    pbase_n[p] = s_in + pbase + (hsel ? 8 : 0);               // + the upper half's K group: next in the row ...
+    pbase_w[p] = s_in + pbase + (hsel ? kInPitch - 16 : 0);   // ... or first of the next row (load_b)
+  }
+
+  // patch dwords of a tile: unconditional loads from a clamped address, so none waits for the previous one
   unsigned pv[kInIters];
   bool pok[kInIters];
-  auto patch_issue = [&](int t) {
-    const int tx = t % tiles_x;
-    const int ty = (t / tiles_x) % tiles_y, b = t / (tiles_x * tiles_y);
+  const int64_t poff = pr0 * row_bytes + 4 * pd;         // the thread's first dword from the patch's (row 0, dword 0)
+  auto patch_issue = [&](int tx, int ty, int b) {
     const int iy0 = 2 * (16 * ty - 1) - 3;               // input origin: row 32*ty - 5
     const int64_t a0 = 96 * (int64_t)tx - 16;            // aligned byte offset inside an image row (x origin = 32*tx - 5 -> byte -15)
+    const int64_t bo = a0 + 4 * pd;
+    const bool colok = bo >= 0 && bo < row_bytes;
+    const int64_t origin = ((int64_t)b * H + iy0) * row_bytes + a0;      // (uniform; may lie in front of the image)
 #pragma unroll
     for (int it = 0; it < kInIters; it++) {
-      const int item = tid + 256 * it, r = item / kInDw, d = item % kInDw;
-      const int iy = iy0 + r;
-      const int64_t bo = a0 + 4 * d;
-      pok[it] = r < 39 && iy >= 0 && iy < H && bo >= 0 && bo < row_bytes;
-      pv[it] = *reinterpret_cast<const unsigned*>(img + (pok[it] ? ((int64_t)b * H + iy) * row_bytes + bo : 0));
+      const int r = pr0 + 8 * it, iy = iy0 + r;
+      pok[it] = colok && r < 39 && iy >= 0 && iy < H;
+      pv[it] = *reinterpret_cast<const unsigned*>(img + (pok[it] ? origin + 8 * it * row_bytes + poff : 0));
     }
   };
   int t = blockIdx.x;
-  patch_issue(t);
+  int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, b = t / (tiles_x * tiles_y);
+  patch_issue(tx, ty, b);
   for (int i = tid; i < kWBytes / 16; i += 256)
     *reinterpret_cast<f16x8*>(smem + 640 + i * 16) = *reinterpret_cast<const f16x8*>(wp + i * 8);
   s_lut[tid] = (_Float16)((float)tid / divisor);
   if (tid < 64) s_bias[tid] = bias ? bias[tid] : (_Float16)0.f;
-  const int hsel = lane >> 5;
+  __syncthreads();
+  h4 bq[3][4];                        // accumulator row (rq, e) of map half m = channel 32 m + 8 rq + 4 hsel + e; [2]: half m3
+#pragma unroll
+  for (int m = 0; m < 3; m++)
+#pragma unroll
+    for (int rq = 0; rq < 4; rq++)
+      bq[m][rq] = *reinterpret_cast<const h4*>(s_bias + (m < 2 ? m : m3) * 32 + 8 * rq + 4 * hsel);
 
   for (; t < tiles; t += gridDim.x) {
-    const int tx = t % tiles_x;
-    const int ty = (t / tiles_x) % tiles_y, b = t / (tiles_x * tiles_y);
-    const int cy0 = 16 * ty - 1, cx0 = 16 * tx - 1;      // conv-output origin of the tile
-    __syncthreads();      // table / bias / filter visible (first tile); the previous tile's pooling has read the conv tile
+    const int ctx = tx, cty = ty, cb = b;                // this tile; (tx, ty, b) move on to the next one below
+    const int cy0 = 16 * cty - 1, cx0 = 16 * ctx - 1;    // conv-output origin of the tile
+    __syncthreads();      // the previous tile's pooling has read the conv tile
+    _Float16 hv[kInIters][4];
 #pragma unroll
     for (int it = 0; it < kInIters; it++) {
-      const int item = tid + 256 * it, r = item / kInDw, d = item % kInDw;
-      if (item < kInRows * kInDw) {
+      const unsigned v = pok[it] ? pv[it] : 0u;          // outside the image: table entry 0 = +0
 #pragma unroll
-        for (int e = 0; e < 4; e++) {
-          const int j = 4 * d + e - 1;    // half index inside the patch row (byte -15 of the row = index 0)
-          if (j >= 0) s_in[r * kInPitch + j] = pok[it] ? s_lut[(pv[it] >> (8 * e)) & 255u] : (_Float16)0.f;
-        }
-      }
+      for (int e = 0; e < 4; e++) hv[it][e] = s_lut[(v >> (8 * e)) & 255u];
     }
-    // columns 123..135 of every row are read by nobody (max index 119); nothing to clear
-    if (t + (int)gridDim.x < tiles) patch_issue(t + gridDim.x);          // next tile's patch: in flight from here on
+#pragma unroll
+    for (int it = 0; it < kInIters; it++) {              // (all gathers first: a store in between would order them)
+      _Float16* dst = s_in + (pr0 + 8 * it) * kInPitch + 4 * pd;   // halves 4d-1 .. 4d+2 of the row (byte -15 of the row = index 0)
+      dst[-1] = hv[it][0];                               // d = 0: the previous row's unused tail / the lead bytes
+      *reinterpret_cast<h2*>(dst) = h2{hv[it][1], hv[it][2]};
+      dst[2] = hv[it][3];
+    }
+    // columns 127..135 of every row are read by nobody (max index 119); nothing to clear
+    if (t + (int)gridDim.x < tiles) {                    // next tile's patch: in flight from here on
+      const int tn = t + gridDim.x;
+      tx = tn % tiles_x, ty = (tn / tiles_x) % tiles_y, b = tn / (tiles_x * tiles_y);
+      patch_issue(tx, ty, b);
+    }
     __syncthreads();
 
-    // ---- implicit GEMM on the matrix cores: wave w owns pixel tiles w, w+4, w+8 (10 tiles of 32 = 320 >= 289)
-    f32x16 acc[2][3];
+    // ---- implicit GEMM on the matrix cores, one straight line: acc[2 p + m] = maps 32 m .. of pixel tile p (p < 2),
+    // acc[4] = maps 32 m3 .. of the third.  The fragments of step s + 1 are read while step s multiplies.
+    f32x16 acc[5];
 #pragma unroll
-    for (int m = 0; m < 2; m++)
+    for (int u = 0; u < 5; u++)
 #pragma unroll
-      for (int q = 0; q < 3; q++)
+      for (int r = 0; r < 16; r++) acc[u][r] = 0.f;
+    const char* wa_lane = s_w + lane * 16;
+    auto load_a = [&](int s, int m) {                    // m == 2: half m3
+      return *reinterpret_cast<const f16x8*>(wa_lane + ((m < 2 ? m : m3) * kKSteps + s) * 1024);
+    };
+    auto load_b = [&](int s, int p) {
+      // K group kq = 2 s + hsel of the lane's half: ky = kq / 3, g = kq % 3.  The upper half's group lies 8 halfs
+      // behind the lower one's, or at the start of the next patch row when that one is the row's last: two lane-
+      // dependent bases per pixel tile, and the step is a constant offset
+      const int k0 = 2 * s, koff = (k0 / 3) * kInPitch + 8 * (k0 % 3);
+      const unsigned* src = reinterpret_cast<const unsigned*>((k0 % 3 == 2 ? pbase_w[p] : pbase_n[p]) + koff);
+      const u32x4 raw = {src[0], src[1], src[2], src[3]};
+      return __builtin_bit_cast(f16x8, raw);
+    };
+    f16x8 wa[2][3], pf[2][3];
 #pragma unroll
-        for (int r = 0; r < 16; r++) acc[m][q][r] = 0.f;
-    int pbase[3];
-#pragma unroll
-    for (int q = 0; q < 3; q++) {
-      int n = (wave + 4 * q) * 32 + (lane & 31);
-      n = n < 289 ? n : 0;
-      pbase[q] = (2 * (n / 17)) * kInPitch + 6 * (n % 17);     // half index of tap (0,0), channel 0
-    }
+    for (int k = 0; k < 3; k++) wa[0][k] = load_a(0, k), pf[0][k] = load_b(0, k);
 #pragma unroll
     for (int s = 0; s < kKSteps; s++) {
-      const int kq = 2 * s + hsel, ky = kq / 3, g = kq % 3;
-      const int koff = ky * kInPitch + 8 * g;
-      f16x8 wa[2];
+      const int c = s & 1;
+      if (s + 1 < kKSteps) {
 #pragma unroll
-      for (int m = 0; m < 2; m++) wa[m] = *reinterpret_cast<const f16x8*>(s_w + ((m * kKSteps + s) * 64 + lane) * 16);
+        for (int k = 0; k < 3; k++) wa[c ^ 1][k] = load_a(s + 1, k), pf[c ^ 1][k] = load_b(s + 1, k);
+      }
 #pragma unroll
-      for (int q = 0; q < 3; q++) {
-        if ((wave + 4 * q) * 32 >= 289) continue;            // wave-uniform
-        const unsigned* src = reinterpret_cast<const unsigned*>(s_in + pbase[q] + koff);
-        u32x4 raw = {src[0], src[1], src[2], src[3]};
-        const f16x8 pf = __builtin_bit_cast(f16x8, raw);
+      for (int p = 0; p < 2; p++)
 #pragma unroll
         for (int m = 0; m < 2; m++)
-          acc[m][q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wa[m], pf, acc[m][q], 0, 0, 0);
-      }
+          acc[2 * p + m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wa[c][m], pf[c][p], acc[2 * p + m], 0, 0, 0);
+      acc[4] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wa[c][2], pf[c][2], acc[4], 0, 0, 0);
     }
     __syncthreads();                                          // patch dead -> conv staging may overwrite it
 
     // ---- bias + ReLU -> LDS, zero where the conv pixel lies outside the conv output (the pool's padding:
     // after ReLU every real value is >= 0 and the window always holds its in-range centre, so 0 == -inf here)
-#pragma unroll
-    for (int q = 0; q < 3; q++) {
-      const int n = (wave + 4 * q) * 32 + (lane & 31);
-      if (n >= 289) continue;
-      const int cy = cy0 + n / 17, cx = cx0 + n % 17;
+    auto stage = [&](const f32x16& a, const h4 (&bh)[4], int p, int m) {
+      const int cy = cy0 + ny[p], cx = cx0 + nx[p];
       const bool in = cy >= 0 && cy < Hc && cx >= 0 && cx < Wc;
+      char* dst = s_conv + (ny[p] * 17 + nx[p]) * kConvPitch + 8 * hsel + m * 64;
+      const h2 zero = {(_Float16)0.f, (_Float16)0.f};
 #pragma unroll
-      for (int m = 0; m < 2; m++)
+      for (int rq = 0; rq < 4; rq++) {
+        h2 lo = {(_Float16)(a[rq * 4] + (float)bh[rq][0]), (_Float16)(a[rq * 4 + 1] + (float)bh[rq][1])};
+        h2 hi = {(_Float16)(a[rq * 4 + 2] + (float)bh[rq][2]), (_Float16)(a[rq * 4 + 3] + (float)bh[rq][3])};
+        lo = __builtin_elementwise_max(lo, zero);
+        hi = __builtin_elementwise_max(hi, zero);
+        const h4 v4 = {lo[0], lo[1], hi[0], hi[1]};
+        *reinterpret_cast<h4*>(dst + 16 * rq) = in ? v4 : h4{(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
+      }
+    };
 #pragma unroll
-        for (int rq = 0; rq < 4; rq++) {
-          const int ch = m * 32 + 8 * rq + 4 * hsel;
-          const h4 bq = *reinterpret_cast<const h4*>(s_bias + ch);
-          h4 v4;
+    for (int p = 0; p < 2; p++)
 #pragma unroll
-          for (int e = 0; e < 4; e++) {
-            float v = fmaxf(acc[m][q][rq * 4 + e] + (float)bq[e], 0.f);
-            v4[e] = in ? (_Float16)v : (_Float16)0.f;
-          }
-          *reinterpret_cast<h4*>(s_conv + n * kConvPitch + ch * 2) = v4;
-        }
-    }
+      for (int m = 0; m < 2; m++) stage(acc[2 * p + m], bq[m], p, m);
+    if (nok3) stage(acc[4], bq[2], 2, m3);
     __syncthreads();
 
     // ---- 3x3 / stride 2 max over the staged conv tile, 8 channels (16 B) per item
@@ -184,19 +244,20 @@ __global__ __launch_bounds__(256, 2) void k_stem(const uint8_t* __restrict__ img
     for (int it = 0; it < 2; it++) {
       const int item = tid + 256 * it, pp = item >> 3, cg = item & 7;
       const int py = pp >> 3, px = pp & 7;
-      const int oy = 8 * ty + py, ox = 8 * tx + px;
-      f16x8 mx = *reinterpret_cast<const f16x8*>(s_conv + ((2 * py) * 17 + 2 * px) * kConvPitch + cg * 16);
+      const int oy = 8 * cty + py, ox = 8 * ctx + px;
+      const char* win = s_conv + ((2 * py) * 17 + 2 * px) * kConvPitch + cg * 16;
+      // the staged halves are >= +0 and never NaN (ReLU above), so their order as 16-bit integers is their order
+      // as numbers: a packed integer max, which unlike the f16 one needs no canonicalised operands
+      i16x8 mx = *reinterpret_cast<const i16x8*>(win);
 #pragma unroll
       for (int dy = 0; dy < 3; dy++)
 #pragma unroll
         for (int dx = 0; dx < 3; dx++) {
           if (dy == 0 && dx == 0) continue;
-          const f16x8 v = *reinterpret_cast<const f16x8*>(s_conv + ((2 * py + dy) * 17 + 2 * px + dx) * kConvPitch + cg * 16);
-#pragma unroll
-          for (int e = 0; e < 8; e++) mx[e] = v[e] > mx[e] ? v[e] : mx[e];
+          mx = __builtin_elementwise_max(mx, *reinterpret_cast<const i16x8*>(win + (dy * 17 + dx) * kConvPitch));
         }
       if (oy < Hp && ox < Wp)
-        *reinterpret_cast<f16x8*>(out + (((int64_t)b * Hp + oy) * Wp + ox) * 64 + cg * 8) = mx;
+        *reinterpret_cast<i16x8*>(out + (((int64_t)cb * Hp + oy) * Wp + ox) * 64 + cg * 8) = mx;
     }
   }
 }
