@@ -12,8 +12,7 @@ import torch.nn as nn
 from torch.nn.modules.utils import _pair
 
 from . import _lib
-from .dcn import (DeformConv, _fused_backward, _fused_backward_ok, _is_nhwc, deform_conv_backward_input_cuda,
-                  deform_conv_backward_parameters_cuda)
+from .dcn import DeformConv, _is_nhwc, deform_conv_backward
 
 
 def align_offsets(anchors, featmap_size, stride, kernel_size=3):
@@ -70,8 +69,9 @@ def align_conv_forward(x, anchors, weight, stride, relu=True, packed=False, out_
 class AlignConvFunction(torch.autograd.Function):
     """the fused AlignConv (align_conv_forward, ReLU included) with a backward: the sampling offsets are rebuilt with
     align_offsets (the ones the unfused route feeds deform_conv), grad_output is masked by the saved output (zero where
-    out <= 0, so it passes at a NaN, as torch's ReLU), and the deformable-conv backward of DeformConvFunction gives the input and weight gradients.  The
-    anchors get none (they are detached in the reference, models/head.py:322)."""
+    out <= 0, so it passes at a NaN, as torch's ReLU), and the deformable-conv backward of DeformConvFunction
+    (dcn.deform_conv_backward, which alone decides the route) gives those of the input and weight gradients that are wanted.
+    The anchors get none (they are detached in the reference, models/head.py:322)."""
 
     @staticmethod
     def forward(ctx, x, anchors, weight, stride):
@@ -88,28 +88,10 @@ class AlignConvFunction(torch.autograd.Function):
         B, C, H, W = x.shape
         offset = align_offsets(anchors.detach().reshape(B, H * W, 5), (H, W), ctx.stride, 3)
         go = grad_output.masked_fill(out <= 0, 0)
-        w = weight.type_as(x)
         one = (1, 1)
-        fused = _fused_backward_ok(x, offset, w, go, one, one, one, 1, 1)
-        if _lib.deterministic() and not ctx.needs_input_grad[0] and not (fused and x.dtype == torch.float16):
-            # deterministic mode refuses the routes whose input gradient is a sum of float atomics (everything but the fused
-            # f16 one); a backward that does not want the input gradient takes none of them: the filter's gradient alone
-            gw = None
-            if ctx.needs_input_grad[2]:
-                gw = torch.zeros_like(w)
-                deform_conv_backward_parameters_cuda(x, offset, go, gw, None, None, 3, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, min(64, B))
-                gw = gw.to(weight.dtype)
-            return None, None, gw, None
-        if fused:
-            gin, _, gw = _fused_backward(x, offset, w, go)
-        else:
-            cur = min(64, B)
-            args = (3, 3, 1, 1, 1, 1, 1, 1, 1, 1)
-            gin = torch.zeros_like(x, memory_format=torch.contiguous_format)
-            deform_conv_backward_input_cuda(x, offset, go, gin, torch.zeros_like(offset), w, None, *args, cur)
-            gw = torch.zeros_like(w)
-            deform_conv_backward_parameters_cuda(x, offset, go, gw, None, None, *args, 1, cur)
-        return gin, None, gw.to(weight.dtype), None
+        gin, _, gw = deform_conv_backward(x, offset, weight.type_as(x), go, one, one, one, 1, 1, 64,
+                                          ctx.needs_input_grad[0], ctx.needs_input_grad[2])
+        return gin, None, None if gw is None else gw.to(weight.dtype), None
 
 
 def align_conv(x, anchors, weight, stride):

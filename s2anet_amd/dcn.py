@@ -32,6 +32,31 @@ def _fast_forward_ok(input, weight, offset, kW, kH, dW, dH, padW, padH, dilation
             and weight.shape[0] % 64 == 0 and B * H * W < (1 << 31))
 
 
+def _shape_check(input, offset, weight, kW, kH, dW, dH, padW, padH, dilationW, dilationH, group, deformable_group):
+    """the reference's shape_check (deform_conv_cuda.cpp:62-150) on input, offset and weight, in front of the forward and of both
+    backward entry points; a 3-D input / offset counts as a batch of one.  -> (B, C, H, W, O, Ho, Wo)"""
+    if input.dim() not in (3, 4):
+        raise RuntimeError("3D or 4D input tensor expected but got: %d" % input.dim())
+    if weight.dim() != 4:
+        raise RuntimeError("4D weight tensor (nOutputPlane,nInputPlane,kH,kW) expected, but got: %d" % weight.dim())
+    if weight.size(2) != kH or weight.size(3) != kW:
+        raise RuntimeError("kernel size should be consistent with weight")
+    B, C, H, W = input.shape if input.dim() == 4 else (1, *input.shape)
+    off_shape = tuple(offset.shape) if offset.dim() == 4 else (1, *offset.shape)
+    if weight.shape[1] * group != C:
+        raise RuntimeError("invalid number of input planes, expected: %d, but got: %d" % (weight.shape[1] * group, C))
+    Ho = (H + 2 * padH - (dilationH * (kH - 1) + 1)) // dH + 1
+    Wo = (W + 2 * padW - (dilationW * (kW - 1) + 1)) // dW + 1
+    if off_shape[0] != B:
+        raise RuntimeError("invalid batch size of offset")
+    if off_shape[1] != deformable_group * 2 * kH * kW:
+        raise RuntimeError("invalid number of channels of offset")
+    if off_shape[2:] != (Ho, Wo):
+        raise RuntimeError("invalid spatial size of offset, expected height: %d width: %d, but got "
+                           "height: %d width: %d" % (Ho, Wo, off_shape[2], off_shape[3]))
+    return B, C, H, W, weight.shape[0], Ho, Wo
+
+
 def deform_conv_forward_cuda(input, weight, offset, output, columns, ones, kW, kH, dW, dH, padW,
                              padH, dilationW, dilationH, group, deformable_group, im2col_step,
                              relu=False):
@@ -40,14 +65,9 @@ def deform_conv_forward_cuda(input, weight, offset, output, columns, ones, kW, k
     caller-allocated and filled in place; ``columns`` / ``ones`` / ``im2col_step`` are accepted
     and ignored (the fused kernel has no columns buffer).  Returns 1."""
     _lib.require_cuda(input, weight, offset, output)
-    if input.dim() not in (3, 4):
-        raise RuntimeError("3D or 4D input tensor expected but got: %d" % input.dim())
-    if weight.dim() != 4:
-        raise RuntimeError("4D weight tensor (nOutputPlane,nInputPlane,kH,kW) expected, but got: %d" % weight.dim())
-    if weight.size(2) != kH or weight.size(3) != kW:
-        raise RuntimeError("kernel size should be consistent with weight")
-    squeeze = input.dim() == 3
-    if squeeze:
+    B, C, H, W, O, Ho, Wo = _shape_check(input, offset, weight, kW, kH, dW, dH, padW, padH, dilationW, dilationH, group,
+                                         deformable_group)
+    if input.dim() == 3:
         input, offset, output = input.unsqueeze(0), offset.unsqueeze(0), output.unsqueeze(0)
     off = offset.contiguous()
     if input.dtype == torch.float64:
@@ -63,19 +83,6 @@ def deform_conv_forward_cuda(input, weight, offset, output, columns, ones, kW, k
     w = weight.contiguous()
     if w.dtype != x.dtype:
         w = w.to(x.dtype)
-    B, C, H, W = x.shape
-    O = w.shape[0]
-    if w.shape[1] * group != C:
-        raise RuntimeError("invalid number of input planes, expected: %d, but got: %d" % (w.shape[1] * group, C))
-    Ho = (H + 2 * padH - (dilationH * (kH - 1) + 1)) // dH + 1
-    Wo = (W + 2 * padW - (dilationW * (kW - 1) + 1)) // dW + 1
-    if off.shape[0] != B:
-        raise RuntimeError("invalid batch size of offset")
-    if off.shape[1] != deformable_group * 2 * kH * kW:
-        raise RuntimeError("invalid number of channels of offset")
-    if off.shape[2] != Ho or off.shape[3] != Wo:
-        raise RuntimeError("invalid spatial size of offset, expected height: %d width: %d, but got "
-                           "height: %d width: %d" % (Ho, Wo, off.shape[2], off.shape[3]))
     if tuple(output.shape) != (B, O, Ho, Wo):
         raise RuntimeError("output has the wrong shape")
     out = output if (nhwc or output.is_contiguous()) else torch.empty_like(output, memory_format=torch.contiguous_format)
@@ -96,26 +103,11 @@ def _bwd_common(input, offset, gradOutput, weight_like, kW, kH, dW, dH, padW, pa
                 group, deformable_group, im2col_step):
     """shape_check + views shared by the two backward entry points (deform_conv_cuda.cpp:62-150)"""
     _lib.require_cuda(input, offset, gradOutput, weight_like)
-    if input.dim() not in (3, 4):
-        raise RuntimeError("3D or 4D input tensor expected but got: %d" % input.dim())
-    if weight_like.dim() != 4 or weight_like.size(2) != kH or weight_like.size(3) != kW:
-        raise RuntimeError("kernel size should be consistent with weight")
+    B, C, H, W, O, Ho, Wo = _shape_check(input, offset, weight_like, kW, kH, dW, dH, padW, padH, dilationW, dilationH, group,
+                                         deformable_group)
     x = (input if input.dim() == 4 else input.unsqueeze(0)).contiguous()
     off = (offset if offset.dim() == 4 else offset.unsqueeze(0)).to(x.dtype).contiguous()
     go = (gradOutput if gradOutput.dim() == 4 else gradOutput.unsqueeze(0)).to(x.dtype).contiguous()
-    B, C, H, W = x.shape
-    if weight_like.shape[1] * group != C:
-        raise RuntimeError("invalid number of input planes, expected: %d, but got: %d" % (weight_like.shape[1] * group, C))
-    Ho = (H + 2 * padH - (dilationH * (kH - 1) + 1)) // dH + 1
-    Wo = (W + 2 * padW - (dilationW * (kW - 1) + 1)) // dW + 1
-    if off.shape[0] != B:
-        raise RuntimeError("invalid batch size of offset")
-    if off.shape[1] != deformable_group * 2 * kH * kW:
-        raise RuntimeError("invalid number of channels of offset")
-    if tuple(off.shape[2:]) != (Ho, Wo):
-        raise RuntimeError("invalid spatial size of offset, expected height: %d width: %d, but got "
-                           "height: %d width: %d" % (Ho, Wo, off.shape[2], off.shape[3]))
-    O = weight_like.shape[0]
     if tuple(go.shape) != (B, O, Ho, Wo):
         raise RuntimeError("invalid size of gradOutput")
     assert B % im2col_step == 0, "im2col step must divide batchsize"
@@ -191,6 +183,47 @@ def _cache_step(step, bytes_per_image):
     return best
 
 
+# kW, kH, dW, dH, padW, padH, dilationW, dilationH, group, deformable_group of AlignConv's deformable convolution
+_ALIGN_GEOMETRY = (3, 3, 1, 1, 1, 1, 1, 1, 1, 1)
+# channels up to which the fused weight gradient is taken.  The library would take up to 6784 (3 * (C / 64) <= its 320
+# partial blocks); no test runs the fused weight gradient above 4096, so wider filters keep the unfused route
+_FUSED_WGRAD_MAX_CHANNELS = 4096
+
+
+def _fused_bwd_ok(dtype, geometry, C, O, H, W, want_input, want_weight):
+    """do the fused AlignConv-geometry backward kernels (fused_bwd_run of csrc/dcn_bwd_ops.hip) serve a call that wants these
+    gradients?  The one statement of their limits on this side; `geometry` in the order of _ALIGN_GEOMETRY.
+    S2A_DCN_BWD_UNFUSED sends every call to the unfused kernels (the tests' reference route)."""
+    return (dtype in (torch.float16, torch.float32) and tuple(geometry) == _ALIGN_GEOMETRY
+            and H >= 3 and W >= 3 and O <= 256
+            and (not want_input or (C % 32 == 0 and O % 16 == 0))
+            and (not want_weight or (C % 64 == 0 and O % 32 == 0 and C <= _FUSED_WGRAD_MAX_CHANNELS))
+            and not os.environ.get("S2A_DCN_BWD_UNFUSED"))
+
+
+def _fused_bwd_call(x, off, go, w, gin, goff, gw, scale=1.0, typed=False):
+    """the one caller of the fused backward: x, off, go (and w, with the input gradient) contiguous NCHW tensors of one type,
+    f16 or f32, inside _fused_bwd_ok.  gin None: no input / offset gradient; else f32 [B,C,H,W], added into (typed: of x's
+    type, overwritten), and goff [B,18,H,W] of x's type, overwritten.  gw None: no weight gradient; else f32 [O,C,3,3],
+    += scale * gradient.  The workspace asked for is that of the gradients wanted, no more."""
+    L, code = _lib.lib(), _lib.dtype_code(x)
+    (B, C, H, W), O = x.shape, go.shape[1]
+    f32 = x.dtype == torch.float32
+    if gin is not None and gw is not None:
+        nbytes = L.s2a_deform_conv_backward_workspace_bytes(code, B, C, H, W, O)
+    elif gin is not None:
+        query = L.s2a_deform_conv_backward_input_f32_workspace_bytes if f32 else L.s2a_deform_conv_backward_input_workspace_bytes
+        nbytes = query(B, C, H, W, O)
+    else:
+        query = L.s2a_deform_conv_backward_weight_f32_workspace_bytes if f32 else L.s2a_deform_conv_backward_weight_workspace_bytes
+        nbytes = query(B, C, H, W, O)
+    ws = _lib.workspace(nbytes, x.device, "dcn_bwd")
+    entry = L.s2a_deform_conv_backward_typed if typed else L.s2a_deform_conv_backward
+    with torch.cuda.device(x.device):
+        _lib.check(entry(code, _lib.ptr(x), _lib.ptr(off), _lib.ptr(go), _lib.ptr(w), _lib.ptr(gin), _lib.ptr(goff), _lib.ptr(gw),
+                         float(scale), B, C, H, W, O, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device)))
+
+
 def _no_deterministic_form(what, why):
     """deterministic mode (s2anet_amd.deterministic): a route whose input gradient is a sum of float atomics is refused, in
     front of its first launch -- the caller's gradient buffers stay as they are"""
@@ -203,10 +236,9 @@ def deform_conv_backward_input_cuda(input, offset, gradOutput, gradInput, gradOf
                                     dW, dH, padW, padH, dilationW, dilationH, group, deformable_group,
                                     im2col_step):
     """models/dcn/src/deform_conv_cuda.cpp:262-374, same positional signature.  gradInput (caller-zeroed,
-    deform_conv.py:88) and gradOffset are filled in place.  AlignConv geometry (3x3, stride 1, pad 1, one group, C % 32 == 0,
-    O % 16 == 0, O <= 256): one fused kernel per call, f32 or f16, no `columns`.  Any other geometry, per chunk of
-    im2col_step images: columns = weight^T x gradOutput (library GEMM, the reference's addmm_ :323), then
-    s2a_deformable_col2im_coord -> gradOffset and s2a_deformable_col2im -> gradInput.  Returns 1."""
+    deform_conv.py:88) and gradOffset are filled in place.  Inside _fused_bwd_ok: one fused kernel per call, f32 or f16, no
+    `columns`.  Any other call, per chunk of im2col_step images: columns = weight^T x gradOutput (library GEMM, the
+    reference's addmm_ :323), then s2a_deformable_col2im_coord -> gradOffset and s2a_deformable_col2im -> gradInput.  Returns 1."""
     x, off, go, (B, C, H, W, O, Ho, Wo), params = _bwd_common(
         input, offset, gradOutput, weight, kW, kH, dW, dH, padW, padH, dilationW, dilationH, group,
         deformable_group, im2col_step)
@@ -215,15 +247,14 @@ def deform_conv_backward_input_cuda(input, offset, gradOutput, gradInput, gradOf
     step, npos = im2col_step, im2col_step * Ho * Wo
     p = params(step)
     goff = torch.empty_like(off)
-    align_geom = ((kW, kH, dW, dH, padW, padH, dilationW, dilationH) == (3, 3, 1, 1, 1, 1, 1, 1) and group == 1
-                  and deformable_group == 1 and C % 32 == 0 and O % 16 == 0 and O <= 256 and H >= 3 and W >= 3
-                  and not os.environ.get("S2A_DCN_BWD_UNFUSED"))
-    if _lib.deterministic() and not (align_geom and x.dtype == torch.float16):
+    fused = _fused_bwd_ok(x.dtype, (kW, kH, dW, dH, padW, padH, dilationW, dilationH, group, deformable_group), C, O, H, W,
+                          want_input=True, want_weight=False)
+    if _lib.deterministic() and not (fused and x.dtype == torch.float16):
         _no_deterministic_form("deform_conv_backward_input", "the float32 fused kernel adds into gradInput with float atomics"
-                               if align_geom else "the unfused deformable_col2im scatters with float atomics")
-    # f32 + AlignConv geometry: the fused dataflow on the f32 matrix instruction (s2a_deform_conv_backward_input_f32),
-    # accumulating straight into the caller's gradInput when it is the f32 NCHW tensor deform_conv.py:88 allocates
-    if align_geom and x.dtype == torch.float32:
+                               if fused else "the unfused deformable_col2im scatters with float atomics")
+    # f32, fused: the kernel's atomics add straight into the caller's gradInput when it is the f32 NCHW tensor
+    # deform_conv.py:88 allocates, and gradOffset is written in place likewise; any other tensor is staged
+    if fused and x.dtype == torch.float32:
         direct = (gradInput.dtype == torch.float32 and gradInput.is_contiguous() and gradInput.numel() == B * C * H * W
                   and gradInput.device == x.device)
         gin = gradInput if direct else torch.zeros((B, C, H, W), dtype=torch.float32, device=x.device)
@@ -231,28 +262,18 @@ def deform_conv_backward_input_cuda(input, offset, gradOutput, gradInput, gradOf
                       and gradOffset.device == x.device)
         if direct_off:
             goff = gradOffset
-        ws = _lib.workspace(L.s2a_deform_conv_backward_input_f32_workspace_bytes(B, C, H, W, O), x.device, "dcn_bwd")
-        with torch.cuda.device(x.device):
-            _lib.check(L.s2a_deform_conv_backward_input_f32(_lib.ptr(x), _lib.ptr(off), _lib.ptr(go), _lib.ptr(w), _lib.ptr(gin),
-                                                            _lib.ptr(goff), B, C, H, W, O, _lib.ptr(ws), ws.numel(),
-                                                            _lib.stream_ptr(x.device)))
+        _fused_bwd_call(x, off, go, w, gin, goff, None)
         if not direct:
             gradInput.view(B, C, H, W).add_(gin.to(gradInput.dtype))
         if not direct_off:
             gradOffset.view_as(goff).copy_(goff)
         return 1
-    # f16 + AlignConv geometry: ONE fused kernel for the whole batch -- column gradient on the matrix cores, consumed in
-    # LDS, no `columns` tensor (s2a_deform_conv_backward_input_f16); the chunking by im2col_step has nothing to chunk then
-    if align_geom and x.dtype == torch.float16:
-        nbytes = L.s2a_deform_conv_backward_input_workspace_bytes(B, C, H, W, O)
-        ws = _lib.workspace(nbytes, x.device, "dcn_bwd")
-        # the library sums in f32 and hands the gradient over rounded to f16 once (s2a_deform_conv_backward_typed without the weight
-        # gradient): the same values as an f32 tensor converted here, without the zero-filled f32 copy and its two passes
+    # f16, fused: the library sums in f32 and hands the gradient over rounded to f16 once (the typed call without the weight
+    # gradient): the same values as an f32 tensor converted here, without the zero-filled f32 copy and its two passes.  No
+    # `columns` tensor, so the chunking by im2col_step has nothing to chunk
+    if fused:
         gin16 = torch.empty((B, C, H, W), dtype=torch.float16, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(L.s2a_deform_conv_backward_typed(_lib.dtype_code(x), _lib.ptr(x), _lib.ptr(off), _lib.ptr(go), _lib.ptr(w),
-                                                        _lib.ptr(gin16), _lib.ptr(goff), None, 1.0, B, C, H, W, O, _lib.ptr(ws),
-                                                        ws.numel(), _lib.stream_ptr(x.device)))
+        _fused_bwd_call(x, off, go, w, gin16, goff, None, typed=True)
         gradInput.view(B, C, H, W).add_(gin16.to(gradInput.dtype))
         gradOffset.view_as(goff).copy_(goff)
         return 1
@@ -278,8 +299,8 @@ def deform_conv_backward_input_cuda(input, offset, gradOutput, gradInput, gradOf
 def deform_conv_backward_parameters_cuda(input, offset, gradOutput, gradWeight, columns, ones, kW, kH, dW, dH,
                                          padW, padH, dilationW, dilationH, group, deformable_group, scale,
                                          im2col_step):
-    """models/dcn/src/deform_conv_cuda.cpp:376-489, same positional signature.  AlignConv geometry (3x3, stride 1, pad 1,
-    one group, C % 64 == 0, O % 32 == 0, O <= 256): one fused kernel per call, f32 or f16, no `columns`.  Otherwise, per chunk:
+    """models/dcn/src/deform_conv_cuda.cpp:376-489, same positional signature.  Inside _fused_bwd_ok: one fused kernel per
+    call, f32 or f16, no `columns`.  Otherwise, per chunk:
     columns = s2a_deformable_im2col(input, offset), gradWeight += scale * gradOutput x columns^T (library
     GEMM, the reference's addmm_ :455-459).  gradWeight is accumulated in place.  Returns 1."""
     x, off, go, (B, C, H, W, O, Ho, Wo), params = _bwd_common(
@@ -287,33 +308,22 @@ def deform_conv_backward_parameters_cuda(input, offset, gradOutput, gradWeight, 
         deformable_group, im2col_step)
     L = _lib.lib()
     step = im2col_step
-    # f16 + AlignConv geometry: ONE fused kernel for the whole batch (columns formed and contracted in LDS, positions as the
-    # MFMA's K through transposing LDS reads; every workgroup writes its partial block, k_dcn_bwd_weight_reduce sums them in a
-    # fixed order -- no atomics, bit-reproducible): s2a_deform_conv_backward_weight_f16
-    fused = (x.dtype == torch.float16 and (kW, kH, dW, dH, padW, padH, dilationW, dilationH) == (3, 3, 1, 1, 1, 1, 1, 1)
-             and group == 1 and deformable_group == 1 and C % 64 == 0 and C <= 4096 and O % 32 == 0 and O <= 256 and H >= 3 and W >= 3
-             and not os.environ.get("S2A_DCN_BWD_UNFUSED"))
-    if fused:
+    # fused: ONE kernel for the whole batch (columns formed and contracted in LDS, positions as the MFMA's K; every workgroup
+    # writes its partial block, k_dcn_bwd_weight_reduce sums them in a fixed order -- no atomics, bit-reproducible)
+    fused = _fused_bwd_ok(x.dtype, (kW, kH, dW, dH, padW, padH, dilationW, dilationH, group, deformable_group), C, O, H, W,
+                          want_input=False, want_weight=True)
+    # f16: into a zeroed f32 accumulator, scaled and rounded to the caller's type here
+    if fused and x.dtype == torch.float16:
         acc = torch.zeros((O, C, 3, 3), dtype=torch.float32, device=x.device)
-        ws = _lib.workspace(L.s2a_deform_conv_backward_weight_workspace_bytes(B, C, H, W, O), x.device, "dcn_bwd")
-        with torch.cuda.device(x.device):
-            _lib.check(L.s2a_deform_conv_backward_weight_f16(_lib.ptr(x), _lib.ptr(off), _lib.ptr(go), _lib.ptr(acc), B, C, H, W, O,
-                                                             _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device)))
+        _fused_bwd_call(x, off, go, None, None, None, acc)
         gradWeight.add_((float(scale) * acc).view_as(gradWeight).to(gradWeight.dtype))
         return 1
-    # f32 + AlignConv geometry: the same dataflow on v_mfma_f32_16x16x4_f32 (s2a_deform_conv_backward_weight_f32; partial blocks +
-    # deterministic reduce as well), scaled and accumulated straight into the caller's gradWeight when it is an f32 contiguous tensor
-    fused32 = (x.dtype == torch.float32 and (kW, kH, dW, dH, padW, padH, dilationW, dilationH) == (3, 3, 1, 1, 1, 1, 1, 1)
-               and group == 1 and deformable_group == 1 and C % 64 == 0 and C <= 4096 and O % 32 == 0 and O <= 256 and H >= 3 and W >= 3
-               and not os.environ.get("S2A_DCN_BWD_UNFUSED"))
-    if fused32:
+    # f32: scaled inside the call and accumulated straight into the caller's gradWeight when it is an f32 contiguous tensor
+    if fused:
         direct = (gradWeight.dtype == torch.float32 and gradWeight.is_contiguous() and gradWeight.numel() == O * C * 9
                   and gradWeight.device == x.device)
         acc = gradWeight if direct else torch.zeros((O, C, 3, 3), dtype=torch.float32, device=x.device)
-        ws = _lib.workspace(L.s2a_deform_conv_backward_weight_f32_workspace_bytes(B, C, H, W, O), x.device, "dcn_bwd")
-        with torch.cuda.device(x.device):
-            _lib.check(L.s2a_deform_conv_backward_weight_f32(_lib.ptr(x), _lib.ptr(off), _lib.ptr(go), _lib.ptr(acc), float(scale),
-                                                             B, C, H, W, O, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device)))
+        _fused_bwd_call(x, off, go, None, None, None, acc, scale)
         if not direct:
             gradWeight.add_(acc.view_as(gradWeight).to(gradWeight.dtype))
         return 1
@@ -334,14 +344,14 @@ def deform_conv_backward_parameters_cuda(input, offset, gradOutput, gradWeight, 
 
 
 def _fused_backward_ok(input, offset, weight, grad_output, stride, padding, dilation, groups, deformable_groups):
-    """both gradients in one library call (s2a_deform_conv_backward): AlignConv geometry, f16 / f32, C % 64, O % 32, O <= 256"""
+    """both gradients in one library call (_fused_backward): _fused_bwd_ok for the two of them on a non-empty batch whose
+    offset and grad_output have the input's map size, unless S2A_DCN_BWD_SEPARATE asks for the two entry points"""
     B, C, H, W = input.shape
-    O = weight.shape[0]
-    return (input.dtype in (torch.float16, torch.float32) and tuple(weight.shape[2:]) == (3, 3)
-            and stride == (1, 1) and padding == (1, 1) and dilation == (1, 1) and groups == 1 and deformable_groups == 1
-            and C % 64 == 0 and C <= 4096 and O % 32 == 0 and O <= 256 and H >= 3 and W >= 3 and B > 0
+    O, kH, kW = weight.shape[0], weight.shape[2], weight.shape[3]
+    geometry = (kW, kH, stride[1], stride[0], padding[1], padding[0], dilation[1], dilation[0], groups, deformable_groups)
+    return (_fused_bwd_ok(input.dtype, geometry, C, O, H, W, want_input=True, want_weight=True) and B > 0
             and offset.shape == (B, 18, H, W) and grad_output.shape == (B, O, H, W)
-            and not os.environ.get("S2A_DCN_BWD_UNFUSED") and not os.environ.get("S2A_DCN_BWD_SEPARATE"))
+            and not os.environ.get("S2A_DCN_BWD_SEPARATE"))
 
 
 def _fused_backward(input, offset, weight, grad_output):
@@ -358,14 +368,30 @@ def _fused_backward(input, offset, weight, grad_output):
     gin = torch.empty((B, C, H, W), dtype=dt, device=x.device)           # overwritten, in the input's own type
     goff = torch.empty((B, 18, H, W), dtype=dt, device=x.device)
     gw = torch.zeros((O, C, 3, 3), dtype=torch.float32, device=x.device)
-    L = _lib.lib()
-    code = _lib.dtype_code(x)
-    ws = _lib.workspace(L.s2a_deform_conv_backward_workspace_bytes(code, B, C, H, W, O), x.device, "dcn_bwd")
-    with torch.cuda.device(x.device):
-        _lib.check(L.s2a_deform_conv_backward_typed(code, _lib.ptr(x), _lib.ptr(off), _lib.ptr(go), _lib.ptr(w), _lib.ptr(gin),
-                                                    _lib.ptr(goff), _lib.ptr(gw), 1.0, B, C, H, W, O, _lib.ptr(ws), ws.numel(),
-                                                    _lib.stream_ptr(x.device)))
+    _fused_bwd_call(x, off, go, w, gin, goff, gw, typed=True)
     return gin, goff.to(offset.dtype), gw.to(weight.dtype)
+
+
+def deform_conv_backward(input, offset, weight, grad_output, stride, padding, dilation, groups, deformable_groups, im2col_step,
+                         want_input, want_weight):
+    """models/dcn/deform_conv.py:73-118 -> (grad_input, grad_offset, grad_weight), None where not wanted: the backward of
+    DeformConvFunction and of AlignConvFunction.  Both gradients in one call where _fused_backward_ok, else the reference's two
+    entry points on zeroed tensors, each only if wanted (and each choosing its kernels by _fused_bwd_ok)"""
+    if want_input and want_weight and _fused_backward_ok(input, offset, weight, grad_output, stride, padding, dilation, groups,
+                                                         deformable_groups):
+        return _fused_backward(input, offset, weight, grad_output)
+    cur = min(im2col_step, input.shape[0])                    # (that it divides the batch is asserted by the entry points)
+    kH, kW = weight.shape[2], weight.shape[3]
+    args = (kW, kH, stride[1], stride[0], padding[1], padding[0], dilation[1], dilation[0], groups, deformable_groups)
+    grad_input = grad_offset = grad_weight = None
+    if want_input:
+        grad_input = torch.zeros_like(input, memory_format=torch.contiguous_format)
+        grad_offset = torch.zeros_like(offset, memory_format=torch.contiguous_format)
+        deform_conv_backward_input_cuda(input, offset, grad_output, grad_input, grad_offset, weight, None, *args, cur)
+    if want_weight:
+        grad_weight = torch.zeros_like(weight)
+        deform_conv_backward_parameters_cuda(input, offset, grad_output, grad_weight, None, None, *args, 1, cur)
+    return grad_input, grad_offset, grad_weight
 
 
 class DeformConvFunction(torch.autograd.Function):
@@ -398,30 +424,13 @@ class DeformConvFunction(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
-        """models/dcn/deform_conv.py:73-118"""
         input, offset, weight = ctx.saved_tensors
         stride, padding, dilation, groups, deformable_groups, im2col_step = ctx.conf
         if not grad_output.is_cuda:
             raise NotImplementedError
-        cur = min(im2col_step, input.shape[0])
-        assert (input.shape[0] % cur) == 0, "im2col step must divide batchsize"
-        grad_input = grad_offset = grad_weight = None
-        kH, kW = weight.shape[2], weight.shape[3]
-        args = (kW, kH, stride[1], stride[0], padding[1], padding[0], dilation[1], dilation[0], groups,
-                deformable_groups)
-        want_in, want_w = ctx.needs_input_grad[0] or ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        if want_in and want_w and _fused_backward_ok(input, offset, weight, grad_output, stride, padding, dilation, groups,
-                                                     deformable_groups):
-            return (*_fused_backward(input, offset, weight, grad_output), None, None, None, None, None, None)
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            grad_input = torch.zeros_like(input, memory_format=torch.contiguous_format)
-            grad_offset = torch.zeros_like(offset, memory_format=torch.contiguous_format)
-            deform_conv_backward_input_cuda(input, offset, grad_output, grad_input, grad_offset, weight, None,
-                                            *args, cur)
-        if ctx.needs_input_grad[2]:
-            grad_weight = torch.zeros_like(weight)
-            deform_conv_backward_parameters_cuda(input, offset, grad_output, grad_weight, None, None, *args, 1, cur)
-        return grad_input, grad_offset, grad_weight, None, None, None, None, None, None
+        grads = deform_conv_backward(input, offset, weight, grad_output, stride, padding, dilation, groups, deformable_groups,
+                                     im2col_step, ctx.needs_input_grad[0] or ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+        return (*grads, None, None, None, None, None, None)
 
 
 deform_conv = DeformConvFunction.apply

@@ -108,7 +108,7 @@ def make_case(seed, B, C, O, H, W, stride, dtype, wild=True):
     edge_block(gen, off, max(1, min(H // 4, 8)))
     raw = off
     if dtype == torch.float16:
-        off = off.half().float()                       # _fused_backward hands the kernel f16 offsets (dcn.py:330)
+        off = off.half().float()                       # dcn._fused_backward hands the kernel f16 offsets
     out = deform_conv(x, off.to(dtype), w, 1, 1, 1, 1, 1)
     go = torch.randn((B, O, H, W), device=DEV, generator=gen).to(dtype).masked_fill(out <= 0, 0)
     return x, off, w, go, wild0, raw

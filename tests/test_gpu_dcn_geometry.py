@@ -29,7 +29,7 @@ of the sum sees (u = u32 for f16 and f32 kernels, which compute in f32; u64 for 
   tiny: 1e-30; f16: 2^-25 (half a subnormal step) for an underflowed result plus 2^-25 per underflowed f16 column
       entry times what multiplies it: sum |w| (forward), M (input), the coordinate weights (offset), sum |grad_out|
       (weight).
-Calls that dispatch to the fused kernels (the fast forward, _fused_backward, the align_geom routes) are held to the
+Calls that dispatch to the fused kernels (the fast forward, _fused_backward, the _fused_bwd_ok routes) are held to the
 bounds tests/test_gpu_forward_shapes.py and tests/test_gpu_dcn_backward_shapes.py derive for those kernels, imported
 from there: the point of those cases is that both neighbours of a limit agree with the same reference.
 
@@ -336,8 +336,8 @@ NEEDS = {"input_offset": ("x", "offset"), "weight": ("weight",), "all": ("x", "o
 @pytest.mark.parametrize("dtype", (F32, F16), **DT_IDS)
 @pytest.mark.parametrize("cid", BWD_BOUNDARY)
 def test_backward_dispatch_boundaries(cid, dtype, needs):
-    """both neighbours of the limits of align_geom (C % 32, O % 16, O <= 256), of the fused weight gradient and of
-    _fused_backward_ok (C % 64, O % 32), under every needs_input_grad pattern: the separate entry points and the
+    """both neighbours of the limits of dcn._fused_bwd_ok for the input gradient (C % 32, O % 16, O <= 256), for the weight
+    gradient and for both (_fused_backward_ok: C % 64, O % 32), under every needs_input_grad pattern: the separate entry points and the
     one-call _fused_backward all agree with the same reference"""
     c = G.ALL[cid]
     v = values(c, dtype, f32_offsets=True)            # the forward samples at f32 offsets ...
