@@ -2177,7 +2177,9 @@ def test_head_on_concurrent_streams_matches_serial():
 def test_pyramid_topk_ties_and_sizes():
     """the per-(image, level) select on heavily tied keys (a handful of distinct logits): exactly k rows, every row
     above the k-th key, the k-th key's rows in ascending position order, positions ascending; levels at, below and
-    above k; 17+ classes take the generic key loop"""
+    above k.  All three cases here run on precomputed keys (k_pyr_keys) except the last, which takes the vector loop of
+    k_pyr_topk: the 20-class case too (25 600 B of keys fit its 69 280 B scores buffer).  The plain key loop for 17+
+    classes is run by tests/test_gpu_glue.py (cases generic17, generic64)"""
     from s2anet_amd import pyramid as P
     from s2anet_amd.pyramid import PyramidLayout
     g = torch.Generator().manual_seed(31)
