@@ -705,6 +705,15 @@ int s2a_conv1x1_chain_f16(const void* x, const void* weight_frag, const void* bi
 int s2a_conv1x1_add_up2_f16(const void* x, const void* weight_frag, const void* bias, const void* coarse,
                             void* out, int64_t batch, int64_t channels, int64_t height, int64_t width,
                             int64_t out_channels, s2a_stream_t stream);
+/* Its training side (FusedConv2d with own_grad_entry, s2anet_amd.fused.FusedConvUp2Function): the forward is the launch
+ * above on the forward filter of s2a_conv_pack_weight_train; the input, weight and bias gradients are those of the 1x1
+ * convolution (s2a_conv_nhwc_f16 on the input-gradient filter, s2a_conv_backward_weight_f16, s2a_conv_backward_prep_f16);
+ * the gradient of coarse is s2a_sum_pool2x2_f16: g[B,H,W,O] f16 -> out[B,H/2,W/2,O] f16,
+ *   out[b,i,j,o] = f16( ((g[b,2i,2j,o] + g[b,2i,2j+1,o]) + g[b,2i+1,2j,o]) + g[b,2i+1,2j+1,o] )   over f32, one rounding.
+ * H and W even, O a multiple of 8, g under 2^31 bytes, both tensors 16-byte aligned; every element of out is written and
+ * nothing else; checked before the first HIP call (S2A_EINVAL with a message). */
+int s2a_sum_pool2x2_f16(const void* g, void* out, int64_t batch, int64_t height, int64_t width, int64_t channels,
+                        s2a_stream_t stream);
 
 /* Pyramid-packed head launches.  The conv towers, AlignConv and prediction heads of S2ANetHead share
  * their filters over the FPN levels (models/head.py:261-265 maps forward_single over the levels), so
@@ -793,6 +802,37 @@ int64_t s2a_stem_packed_elems(void);
 int s2a_stem_pack_weight_f16(const void* weight, void* packed, s2a_stream_t stream);
 int s2a_stem_u8_f16(const void* image_u8, const void* weight_packed, const void* bias, void* out,
                     int64_t batch, int64_t height, int64_t width, float divisor, s2a_stream_t stream);
+
+/* Training side of the stem (FusedConv2d with own_grad_entry, s2anet_amd.fused.StemU8Function): forward from the uint8
+ * batch, filter and bias gradient; the input is an image, so there is no input gradient.  Shapes and limits as
+ * s2a_stem_u8_f16.  Fixed launch sequences without host reads, float atomics or memset nodes, and a fixed summation order:
+ * capturable and bit-identical from call to call.  No workspace: every buffer written is an argument with a stated size.
+ * Every check is made before the first HIP call and answers S2A_EINVAL with a message.
+ * s2a_stem_u8_f16_train: s2a_stem_u8_f16 plus sel, uint8 [B,Hp,Wp,64] (8-byte aligned).  A separate instantiation of the
+ *   kernel: the convolution, bias add and rounding are the inference kernel's, and for a finite filter and bias out has
+ *   its bits.  The epilogue follows torch, not the inference contract (the note at s2a_dcn_params): a NaN pre-activation
+ *   stays NaN through ReLU and pool, +inf stays +inf.  sel[b,py,px,o] = 3 dy + dx in 0 .. 8 names the tap of the
+ *   3x3 / s2 / p1 window the pool took, conv pixel (2 py - 1 + dy, 2 px - 1 + dx), by ATen's rule: dy then dx, a later tap
+ *   replaces the current one only if it is strictly greater or NaN; a tap outside the conv map is never taken.  Writes all
+ *   B*Hp*Wp*64 elements of out and of sel and nothing else.
+ * s2a_stem_backward_slices: the number of slices of the gradient, from the shapes only (the same answer for the same
+ *   shapes); 0 for a problem the entry point refuses (and for batch 0).
+ * s2a_stem_backward_f16: writes partial, f32 [slices][64*147 + 64], all of it and nothing else; partial[s] holds first the
+ *   filter gradient in [64,3,7,7] order, then the 64 bias sums: the f32 sums, in tile order, over the tiles s, s + slices,
+ *   ... (8 x 8 pooled outputs of one image, the forward's tiles; inside a tile in a fixed order) of
+ *     gW[o,c,ky,kx] += m * grad_out[b,py,px,o] * lut(image[b, 2y+ky-3, 2x+kx-3, c]),   gB[o] += m * grad_out[b,py,px,o],
+ *   (y, x) the conv pixel sel names, m = 0 where out <= 0 else 1 (the gradient passes at a NaN output, as in
+ *   s2a_conv_backward_prep_f16), lut(u) = f16(u / divisor), the value the forward multiplied.  A term with m = 0 is selected
+ *   away, not multiplied; a pixel outside the image is not loaded and enters as +0.  Every product is exact in f32 and no
+ *   gradient is rounded before the sums.  A slice without a tile holds exact zeros.  slices must be the query's answer;
+ *   anything else is refused with no buffer touched.  out, sel, grad_out ([B,Hp,Wp,64] f16 / uint8 / f16) and partial
+ *   16-byte aligned.  s2a_conv_backward_weight_s2_reduce(partial, slices, 64*147 + 64, ...) sums the slices in slice order
+ *   into the master dtype. */
+int s2a_stem_u8_f16_train(const void* image_u8, const void* weight_packed, const void* bias, void* out, void* sel,
+                          int64_t batch, int64_t height, int64_t width, float divisor, s2a_stream_t stream);
+int s2a_stem_backward_slices(int64_t batch, int64_t height, int64_t width);
+int s2a_stem_backward_f16(const void* image_u8, const void* out, const void* sel, const void* grad_out, void* partial,
+                          int slices, int64_t batch, int64_t height, int64_t width, float divisor, s2a_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * S2ANet training loss: compute_loss -> compute_loss_single_level of the reference (models/head.py:353-646) for BOTH

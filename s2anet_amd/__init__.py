@@ -13,7 +13,8 @@ from .dcn import DeformConv, DeformConvFunction, deform_conv, deform_conv_forwar
 from .alignconv import AlignConv, AlignConvFunction, align_conv
 from .orn import RotInvPoolFunction, rot_inv_pool, rot_inv_pool_backward
 from .loss import S2ANetLossFunction, s2anet_loss, grid_anchors
-from .fused import drop_weight_caches, train_kernels, train_conv_ok, train_conv_strided_ok, FusedConv2d, FusedConvFunction
+from .fused import drop_weight_caches, train_kernels, train_conv_ok, train_conv_strided_ok, FusedConv2d, FusedConvFunction, \
+    StemU8Function, FusedConvUp2Function, train_up2_ok
 from .scene import tile_grid, chip_names, gather_chips, merge_detections, SceneDetections
 from .evaluate import evaluate_task1, Task1Evaluator, Task1Result, claim_tp_fp
 from .optim import TrainUpdate, reference_param_groups, reference_lr
@@ -29,5 +30,6 @@ __all__ = [
     "evaluate_task1", "Task1Evaluator", "Task1Result", "claim_tp_fp",
     "TrainUpdate", "reference_param_groups", "reference_lr",
     "train_kernels", "train_conv_ok", "train_conv_strided_ok", "FusedConv2d", "FusedConvFunction",
+    "StemU8Function", "FusedConvUp2Function", "train_up2_ok",
     "quantize_weight_e4m3", "calibrate_fp8", "fp8_towers", "deterministic",
 ]

@@ -189,6 +189,7 @@ SYMBOLS = {
     "s2a_conv3x3_tail1x1_f16": (c_int, [c_vp] * 10 + [c_i64] * 7 + [c_vp]),
     "s2a_conv1x1_chain_f16": (c_int, [c_vp] * 8 + [c_i64] * 6 + [c_vp]),
     "s2a_conv1x1_add_up2_f16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp]),
+    "s2a_sum_pool2x2_f16": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp]),
     "s2a_pyramid_pixels": (c_i64, [ctypes.POINTER(Pyramid), c_i64]),
     "s2a_conv3x3_pyramid_f16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int,
                                         ctypes.POINTER(Pyramid), c_vp]),
@@ -210,6 +211,9 @@ SYMBOLS = {
     "s2a_stem_packed_elems": (c_i64, []),
     "s2a_stem_pack_weight_f16": (c_int, [c_vp, c_vp, c_vp]),
     "s2a_stem_u8_f16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_f32, c_vp]),
+    "s2a_stem_u8_f16_train": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_f32, c_vp]),
+    "s2a_stem_backward_slices": (c_int, [c_i64, c_i64, c_i64]),
+    "s2a_stem_backward_f16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_i64, c_i64, c_i64, c_f32, c_vp]),
     "s2a_pyramid_candidates_count": (c_i64, [ctypes.POINTER(Pyramid), c_i64]),
     "s2a_pyramid_candidates": (c_int, [c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(Pyramid), c_int, c_i64, c_f32, c_vp, c_vp, c_vp, c_vp]),
     "s2a_rbox_to_poly": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp]),

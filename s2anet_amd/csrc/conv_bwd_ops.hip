@@ -710,3 +710,41 @@ extern "C" int s2a_conv_backward_weight_s2_reduce(const void* partial, int slice
   S2A_LAUNCH_CHECK();
   return S2A_OK;
 }
+
+// ================================================================= FPN top-down: the gradient of the nearest 2x up-sampling
+namespace {
+// one thread = 8 maps of one coarse pixel: ((g[2i,2j] + g[2i,2j+1]) + g[2i+1,2j]) + g[2i+1,2j+1] over f32, one rounding
+__global__ void k_sum_pool2x2(const _Float16* __restrict__ g, _Float16* __restrict__ out, int Hh, int Wh, int O8, int64_t items) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= items) return;
+  const int c = (int)(e % O8);
+  const int64_t pix = e / O8;
+  const int j = (int)(pix % Wh), i = (int)((pix / Wh) % Hh);
+  const int64_t b = pix / ((int64_t)Wh * Hh);
+  const int64_t row = (int64_t)2 * Wh * O8 * 8;                               // halfs per row of g
+  const _Float16* src = g + ((b * 2 * Hh + 2 * i) * 2 * Wh + 2 * j) * (int64_t)O8 * 8 + c * 8;
+  const f16x8b a0 = *reinterpret_cast<const f16x8b*>(src), a1 = *reinterpret_cast<const f16x8b*>(src + O8 * 8);
+  const f16x8b b0 = *reinterpret_cast<const f16x8b*>(src + row), b1 = *reinterpret_cast<const f16x8b*>(src + row + O8 * 8);
+  f16x8b r;
+#pragma unroll
+  for (int k = 0; k < 8; k++) r[k] = (_Float16)((((float)a0[k] + (float)a1[k]) + (float)b0[k]) + (float)b1[k]);
+  *reinterpret_cast<f16x8b*>(out + e * 8) = r;
+}
+}  // namespace
+
+extern "C" int s2a_sum_pool2x2_f16(const void* g, void* out, int64_t batch, int64_t height, int64_t width, int64_t channels,
+                                   s2a_stream_t stream) {
+  S2A_CHECK_ARG(batch >= 0 && height > 0 && width > 0 && channels > 0, "sum_pool2x2: bad shape");
+  S2A_CHECK_ARG(height % 2 == 0 && width % 2 == 0, "sum_pool2x2: the map must be exactly twice the coarse map");
+  S2A_CHECK_ARG(channels % 8 == 0, "sum_pool2x2: the channel count must be a multiple of 8");
+  S2A_CHECK_ARG(height < (1ll << 24) && width < (1ll << 24) && channels < (1ll << 24) && batch < (1ll << 31) &&
+                (uint64_t)batch * height * width * channels * 2 < (1ull << 31), "sum_pool2x2: tensor too large for 32-bit offsets");
+  if (batch == 0) return S2A_OK;
+  S2A_CHECK_ARG(g && out, "sum_pool2x2: NULL tensor");
+  S2A_CHECK_ARG(aligned16(g) && aligned16(out), "sum_pool2x2: tensors must be 16-byte aligned");
+  const int64_t items = batch * (height / 2) * (width / 2) * (channels / 8);
+  k_sum_pool2x2<<<(unsigned)((items + 255) / 256), 256, 0, as_stream(stream)>>>((const _Float16*)g, (_Float16*)out, (int)(height / 2),
+                                                                                (int)(width / 2), (int)(channels / 8), items);
+  S2A_LAUNCH_CHECK();
+  return S2A_OK;
+}

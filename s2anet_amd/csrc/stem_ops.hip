@@ -79,12 +79,16 @@ __global__ void k_stem_pack(const _Float16* __restrict__ w, _Float16* __restrict
 constexpr int kWBytes = 2 * kKSteps * 64 * 16;                          // 22528
 constexpr int kInLead = 16;                                             // bytes in front of the patch (see above)
 static_assert(kInLead + kInBytes <= kConvBytes, "the patch lies inside the conv staging buffer");
+// kTrain (s2a_stem_u8_f16_train): the same arithmetic up to the rounded pre-activation; then torch's ReLU (a NaN stays a
+// NaN) and ATen's max-pool scan, which also leaves sel[b,py,px,o] = 3 dy + dx, the tap the pool took.
+template <bool kTrain>
 __global__ __launch_bounds__(256, 2) void k_stem(const uint8_t* __restrict__ img,      // [B,H,W,3]
                                                  const _Float16* __restrict__ wp,     // k_stem_pack
                                                  const _Float16* __restrict__ bias,   // [64] or null
                                                  _Float16* __restrict__ out,          // [B,Hp,Wp,64]
                                                  int H, int W, int Hc, int Wc, int Hp, int Wp,
-                                                 int tiles_x, int tiles_y, float divisor, int tiles) {
+                                                 int tiles_x, int tiles_y, float divisor, int tiles,
+                                                 uint8_t* __restrict__ sel) {         // [B,Hp,Wp,64] (kTrain) or null
   extern __shared__ __attribute__((aligned(16))) char smem[];
   _Float16* s_lut = reinterpret_cast<_Float16*>(smem);                 // 256 halfs
   _Float16* s_bias = reinterpret_cast<_Float16*>(smem + 512);          // 64 halfs
@@ -226,8 +230,13 @@ __global__ __launch_bounds__(256, 2) void k_stem(const uint8_t* __restrict__ img
       for (int rq = 0; rq < 4; rq++) {
         h2 lo = {(_Float16)(a[rq * 4] + (float)bh[rq][0]), (_Float16)(a[rq * 4 + 1] + (float)bh[rq][1])};
         h2 hi = {(_Float16)(a[rq * 4 + 2] + (float)bh[rq][2]), (_Float16)(a[rq * 4 + 3] + (float)bh[rq][3])};
+        const h2 plo = lo, phi = hi;
         lo = __builtin_elementwise_max(lo, zero);
         hi = __builtin_elementwise_max(hi, zero);
+        if constexpr (kTrain) {                                 // the max above answers 0 for a NaN: put it back
+          lo = h2{plo[0] != plo[0] ? plo[0] : lo[0], plo[1] != plo[1] ? plo[1] : lo[1]};
+          hi = h2{phi[0] != phi[0] ? phi[0] : hi[0], phi[1] != phi[1] ? phi[1] : hi[1]};
+        }
         const h4 v4 = {lo[0], lo[1], hi[0], hi[1]};
         *reinterpret_cast<h4*>(dst + 16 * rq) = in ? v4 : h4{(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
       }
@@ -246,21 +255,274 @@ __global__ __launch_bounds__(256, 2) void k_stem(const uint8_t* __restrict__ img
       const int py = pp >> 3, px = pp & 7;
       const int oy = 8 * cty + py, ox = 8 * ctx + px;
       const char* win = s_conv + ((2 * py) * 17 + 2 * px) * kConvPitch + cg * 16;
-      // the staged halves are >= +0 and never NaN (ReLU above), so their order as 16-bit integers is their order
-      // as numbers: a packed integer max, which unlike the f16 one needs no canonicalised operands
-      i16x8 mx = *reinterpret_cast<const i16x8*>(win);
+      if constexpr (kTrain) {
+        // ATen's scan (max_pool2d_with_indices): dy then dx over the taps inside the conv map, starting from -inf at the
+        // first of them; a later tap takes over only if it is greater or NaN.  A staged pixel outside the map is never read
+        const int dy0 = oy == 0 ? 1 : 0, dx0 = ox == 0 ? 1 : 0;
+        f16x8 best;
+        unsigned char id[8];
 #pragma unroll
-      for (int dy = 0; dy < 3; dy++)
+        for (int e = 0; e < 8; e++) best[e] = -(_Float16)__builtin_inff(), id[e] = (unsigned char)(3 * dy0 + dx0);
 #pragma unroll
-        for (int dx = 0; dx < 3; dx++) {
-          if (dy == 0 && dx == 0) continue;
-          mx = __builtin_elementwise_max(mx, *reinterpret_cast<const i16x8*>(win + (dy * 17 + dx) * kConvPitch));
+        for (int dy = 0; dy < 3; dy++)
+#pragma unroll
+          for (int dx = 0; dx < 3; dx++) {
+            const int cy = 2 * oy - 1 + dy, cx = 2 * ox - 1 + dx;
+            if (!(cy >= 0 && cy < Hc && cx >= 0 && cx < Wc)) continue;
+            const f16x8 v = *reinterpret_cast<const f16x8*>(win + (dy * 17 + dx) * kConvPitch);
+#pragma unroll
+            for (int e = 0; e < 8; e++)
+              if (v[e] > best[e] || v[e] != v[e]) best[e] = v[e], id[e] = (unsigned char)(3 * dy + dx);
+          }
+        if (oy < Hp && ox < Wp) {
+          const int64_t o = (((int64_t)cb * Hp + oy) * Wp + ox) * 64 + cg * 8;
+          *reinterpret_cast<f16x8*>(out + o) = best;
+          uint2 packed = {0u, 0u};
+#pragma unroll
+          for (int e = 0; e < 4; e++) packed.x |= (unsigned)id[e] << (8 * e), packed.y |= (unsigned)id[4 + e] << (8 * e);
+          *reinterpret_cast<uint2*>(sel + o) = packed;
         }
-      if (oy < Hp && ox < Wp)
-        *reinterpret_cast<i16x8*>(out + (((int64_t)cb * Hp + oy) * Wp + ox) * 64 + cg * 8) = mx;
+      } else {
+        // the staged halves are >= +0 and never NaN (ReLU above), so their order as 16-bit integers is their order
+        // as numbers: a packed integer max, which unlike the f16 one needs no canonicalised operands
+        i16x8 mx = *reinterpret_cast<const i16x8*>(win);
+#pragma unroll
+        for (int dy = 0; dy < 3; dy++)
+#pragma unroll
+          for (int dx = 0; dx < 3; dx++) {
+            if (dy == 0 && dx == 0) continue;
+            mx = __builtin_elementwise_max(mx, *reinterpret_cast<const i16x8*>(win + (dy * 17 + dx) * kConvPitch));
+          }
+        if (oy < Hp && ox < Wp)
+          *reinterpret_cast<i16x8*>(out + (((int64_t)cb * Hp + oy) * Wp + ox) * 64 + cg * 8) = mx;
+      }
     }
   }
 }
+
+// ---- backward of the training stem (s2a_stem_backward_f16): filter and bias gradient, no input gradient.
+// One workgroup = one slice: it walks the forward's tiles s, s + slices, ... (8 x 8 pooled windows each) and keeps the whole
+// [64 maps] x [147 filter taps + the bias column] gradient in its accumulators until the last tile.  Per tile the patch is
+// staged through the table exactly as in the forward, and the gradient is contracted on the matrix cores with
+//   K = (window, pool tap) = 64 x 9:  A[o][k] = the window's grad_out[o] where the pool took this tap and the ReLU passed
+//                                              (SELECTED, else +0: a masked inf or NaN never meets a product),
+//                                     B[k][t] = the patch value under filter tap t of the conv pixel this pool tap names,
+// so every product is one term of the definition, exact in f32, and no gradient is rounded on the way.  Column 147 of B is
+// 1 (the bias sum), columns 148 .. 159 are 0.  Wave w takes the windows of pooled rows 2 w and 2 w + 1 (a quarter of K); the
+// four waves' sums are added in wave order at the end.  t = (c * 7 + ky) * 7 + kx: the gradient's own order.
+constexpr int kGradTaps = 147;
+constexpr int kGradCols = 64 * kGradTaps + 64;      // floats per slice
+constexpr int kBwdMaxSlices = 256;
+constexpr int kGoPitch = 72;                        // halfs per map of the transposed grad_out tile (64 windows + pad)
+constexpr int kSelPitch = 72;                       // bytes per map of the transposed tap tile
+constexpr int kBwdInOff = 512;                      // table in front
+constexpr int kBwdGoOff = 11520;                    // >= kBwdInOff + kInLead + kInBytes
+constexpr int kBwdSelOff = kBwdGoOff + 64 * kGoPitch * 2;
+constexpr int kBwdStage = kBwdSelOff + 64 * kSelPitch;
+constexpr int kBwdRed = 10 * 16 * 64 * 4;           // one wave's accumulators
+constexpr int kBwdLds = kBwdRed > kBwdStage ? kBwdRed : kBwdStage;
+static_assert(kBwdInOff + kInLead + kInBytes <= kBwdGoOff && kBwdLds <= 65536, "backward LDS layout");
+
+__global__ __launch_bounds__(256, 1) void k_stem_bwd(const uint8_t* __restrict__ img,        // [B,H,W,3]
+                                                     const _Float16* __restrict__ out,       // [B,Hp,Wp,64] forward output
+                                                     const uint8_t* __restrict__ sel,        // [B,Hp,Wp,64] pool taps
+                                                     const _Float16* __restrict__ gout,      // [B,Hp,Wp,64]
+                                                     float* __restrict__ partial,            // [slices][kGradCols]
+                                                     int H, int W, int Hp, int Wp, int tiles_x, int tiles_y,
+                                                     float divisor, int tiles) {
+  __shared__ __attribute__((aligned(16))) char smem[kBwdLds];
+  _Float16* s_lut = reinterpret_cast<_Float16*>(smem);
+  _Float16* s_in = reinterpret_cast<_Float16*>(smem + kBwdInOff + kInLead);
+  _Float16* s_go = reinterpret_cast<_Float16*>(smem + kBwdGoOff);
+  uint8_t* s_sel = reinterpret_cast<uint8_t*>(smem + kBwdSelOff);
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 31, hsel = lane >> 5;
+  const int64_t row_bytes = (int64_t)W * 3;
+
+  // the tile's inputs, requested one tile ahead: patch dwords as in k_stem, and 16 maps of one window per thread
+  const int pr0 = tid >> 5, pd = tid & 31;
+  const int win = tid >> 2, cg = tid & 3, lpy = win >> 3, lpx = win & 7;
+  unsigned pv[kInIters];
+  bool pok[kInIters], wok;
+  f16x8 gv[2], ov[2];
+  u32x4 sv;
+  const int64_t poff = pr0 * row_bytes + 4 * pd;
+  auto issue = [&](int tx, int ty, int b) {
+    const int iy0 = 2 * (16 * ty - 1) - 3;
+    const int64_t a0 = 96 * (int64_t)tx - 16;
+    const int64_t bo = a0 + 4 * pd;
+    const bool colok = bo >= 0 && bo < row_bytes;
+    const int64_t origin = ((int64_t)b * H + iy0) * row_bytes + a0;
+#pragma unroll
+    for (int it = 0; it < kInIters; it++) {
+      const int rr = pr0 + 8 * it, iy = iy0 + rr;
+      pok[it] = colok && rr < 39 && iy >= 0 && iy < H;
+      pv[it] = *reinterpret_cast<const unsigned*>(img + (pok[it] ? origin + 8 * it * row_bytes + poff : 0));
+    }
+    const int oy = 8 * ty + lpy, ox = 8 * tx + lpx;
+    wok = oy < Hp && ox < Wp;
+    const int64_t o = wok ? (((int64_t)b * Hp + oy) * Wp + ox) * 64 + 16 * cg : 0;   // (a window outside the map: any valid address)
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+      gv[q] = *reinterpret_cast<const f16x8*>(gout + o + 8 * q);
+      ov[q] = *reinterpret_cast<const f16x8*>(out + o + 8 * q);
+    }
+    sv = *reinterpret_cast<const u32x4*>(sel + o);
+  };
+
+  // per lane, once: where filter tap t = 32 nt + r of its B columns starts in the patch, from the lane's first window row
+  const _Float16* pbase[5];
+#pragma unroll
+  for (int nt = 0; nt < 5; nt++) {
+    const int t = 32 * nt + r;
+    const int c = t / 49, ky = (t % 49) / 7, kx = t % 7;
+    pbase[nt] = s_in + (t < kGradTaps ? ky * kInPitch + kx * 3 + c : 0) + 4 * (2 * wave + hsel) * kInPitch;
+  }
+  const bool real4 = 128 + r < kGradTaps, one4 = 128 + r == kGradTaps;
+
+  f32x16 acc[2][5];
+#pragma unroll
+  for (int m = 0; m < 2; m++)
+#pragma unroll
+    for (int nt = 0; nt < 5; nt++)
+#pragma unroll
+      for (int i = 0; i < 16; i++) acc[m][nt][i] = 0.f;
+
+  int t = blockIdx.x;
+  if (t < tiles) issue(t % tiles_x, (t / tiles_x) % tiles_y, t / (tiles_x * tiles_y));
+  s_lut[tid] = (_Float16)((float)tid / divisor);
+  for (; t < tiles; t += gridDim.x) {
+    __syncthreads();                  // the table is there / the previous tile's fragments have been read
+    {
+      _Float16 hv[kInIters][4];
+#pragma unroll
+      for (int it = 0; it < kInIters; it++) {
+        const unsigned v = pok[it] ? pv[it] : 0u;
+#pragma unroll
+        for (int e = 0; e < 4; e++) hv[it][e] = s_lut[(v >> (8 * e)) & 255u];
+      }
+#pragma unroll
+      for (int it = 0; it < kInIters; it++) {
+        _Float16* dst = s_in + (pr0 + 8 * it) * kInPitch + 4 * pd;
+        dst[-1] = hv[it][0];
+        *reinterpret_cast<h2*>(dst) = h2{hv[it][1], hv[it][2]};
+        dst[2] = hv[it][3];
+      }
+      // the window's 16 maps, transposed to [map][window]; tap 255 (no tap) where the window lies outside the map or the
+      // ReLU did not pass (out <= 0; a NaN output passes, as in s2a_conv_backward_prep_f16)
+#pragma unroll
+      for (int e = 0; e < 16; e++) {
+        const int o = 16 * cg + e;
+        const _Float16 ovv = ov[e >> 3][e & 7];
+        const unsigned tap = (sv[e >> 2] >> (8 * (e & 3))) & 255u;
+        s_go[o * kGoPitch + win] = gv[e >> 3][e & 7];
+        s_sel[o * kSelPitch + win] = (uint8_t)((wok && !(ovv <= (_Float16)0.f)) ? tap : 255u);
+      }
+    }
+    if (t + (int)gridDim.x < tiles) {
+      const int tn = t + gridDim.x;
+      issue(tn % tiles_x, (tn / tiles_x) % tiles_y, tn / (tiles_x * tiles_y));
+    }
+    __syncthreads();
+
+    f16x8 gof[2];
+    uint2 self[2];
+#pragma unroll
+    for (int m = 0; m < 2; m++) {
+      gof[m] = *reinterpret_cast<const f16x8*>(s_go + (32 * m + r) * kGoPitch + 16 * wave + 8 * hsel);
+      self[m] = *reinterpret_cast<const uint2*>(s_sel + (32 * m + r) * kSelPitch + 16 * wave + 8 * hsel);
+    }
+#pragma unroll
+    for (int tap = 0; tap < 9; tap++) {
+      const int dy = tap / 3, dx = tap % 3;
+      f16x8 a[2], bf[5];
+#pragma unroll
+      for (int m = 0; m < 2; m++)
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+          const unsigned sj = ((j < 4 ? self[m].x : self[m].y) >> (8 * (j & 3))) & 255u;
+          a[m][j] = sj == (unsigned)tap ? gof[m][j] : (_Float16)0.f;
+        }
+#pragma unroll
+      for (int nt = 0; nt < 5; nt++) {
+        const _Float16* src = pbase[nt] + 2 * dy * kInPitch + 6 * dx;      // window lpx = j: 12 halfs further each
+#pragma unroll
+        for (int j = 0; j < 8; j++) bf[nt][j] = src[12 * j];
+      }
+#pragma unroll
+      for (int j = 0; j < 8; j++) bf[4][j] = real4 ? bf[4][j] : (one4 ? (_Float16)1.f : (_Float16)0.f);
+#pragma unroll
+      for (int m = 0; m < 2; m++)
+#pragma unroll
+        for (int nt = 0; nt < 5; nt++)
+          acc[m][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[m], bf[nt], acc[m][nt], 0, 0, 0);
+    }
+  }
+
+  // ---- the four waves' sums, ((w0 + w1) + w2) + w3, through LDS (over the dead staging buffers)
+  float* red = reinterpret_cast<float*>(smem);
+  for (int ww = 1; ww < 4; ww++) {
+    __syncthreads();
+    if (wave == ww) {
+#pragma unroll
+      for (int m = 0; m < 2; m++)
+#pragma unroll
+        for (int nt = 0; nt < 5; nt++)
+#pragma unroll
+          for (int i = 0; i < 16; i++) red[((m * 5 + nt) * 16 + i) * 64 + lane] = acc[m][nt][i];
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int m = 0; m < 2; m++)
+#pragma unroll
+        for (int nt = 0; nt < 5; nt++)
+#pragma unroll
+          for (int i = 0; i < 16; i++) acc[m][nt][i] += red[((m * 5 + nt) * 16 + i) * 64 + lane];
+    }
+  }
+  if (wave == 0) {
+    float* dst = partial + (int64_t)blockIdx.x * kGradCols;
+#pragma unroll
+    for (int m = 0; m < 2; m++)
+#pragma unroll
+      for (int nt = 0; nt < 5; nt++) {
+        const int tt = 32 * nt + r;
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+          const int o = 32 * m + (i & 3) + 8 * (i >> 2) + 4 * hsel;      // accumulator row of the 32 x 32 tile
+          if (tt < kGradTaps) dst[o * kGradTaps + tt] = acc[m][nt][i];
+          else if (tt == kGradTaps) dst[64 * kGradTaps + o] = acc[m][nt][i];
+        }
+      }
+  }
+}
+
+// what is wrong with a stem problem, or nullptr: the checks the entry points and the slices query share
+const char* stem_shape_problem(int64_t batch, int64_t height, int64_t width) {
+  if (!(batch >= 0 && height >= 7 && width >= 7)) return "bad shape";
+  if (width % 4 != 0) return "image width must be a multiple of 4 (aligned 32-bit loads of RGB rows)";
+  if (!(height < (1ll << 24) && width < (1ll << 24) && batch < (1ll << 31) && batch * height * width * 3 < (1ll << 40)))
+    return "image too large";
+  return nullptr;
+}
+
+struct StemGeom {
+  int H, W, Hc, Wc, Hp, Wp, tiles_x, tiles_y;
+  int64_t tiles;
+};
+StemGeom stem_geom(int64_t batch, int64_t height, int64_t width) {
+  StemGeom q;
+  q.H = (int)height, q.W = (int)width;
+  q.Hc = (q.H - 1) / 2 + 1, q.Wc = (q.W - 1) / 2 + 1;          // 7x7 / 2 / pad 3
+  q.Hp = (q.Hc - 1) / 2 + 1, q.Wp = (q.Wc - 1) / 2 + 1;        // 3x3 / 2 / pad 1
+  q.tiles_x = (q.Wp + 7) / 8, q.tiles_y = (q.Hp + 7) / 8;
+  q.tiles = batch * q.tiles_x * q.tiles_y;
+  return q;
+}
+inline bool aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
 
 }  // namespace
 }  // namespace s2a
@@ -277,30 +539,67 @@ extern "C" int s2a_stem_pack_weight_f16(const void* weight, void* packed, s2a_st
 
 extern "C" int64_t s2a_stem_packed_elems(void) { return 2 * kKSteps * 64 * 8; }
 
+namespace {
+// both forwards: s2a_stem_u8_f16 (sel == nullptr, train == false) and s2a_stem_u8_f16_train
+int stem_forward(const char* who, bool train, const void* image_u8, const void* weight_packed, const void* bias, void* out,
+                 void* sel, int64_t batch, int64_t height, int64_t width, float divisor, s2a_stream_t stream) {
+  S2A_CHECK_ARG(batch >= 0 && height >= 7 && width >= 7, "%s: bad shape", who);
+  S2A_CHECK_ARG(width % 4 == 0, "%s: image width must be a multiple of 4 (aligned 32-bit loads of RGB rows)", who);
+  S2A_CHECK_ARG(divisor > 0, "%s: divisor must be positive", who);
+  S2A_CHECK_ARG(batch * height * width * 3 < (1ll << 40), "%s: image too large", who);
+  if (batch == 0) return S2A_OK;
+  S2A_CHECK_ARG(image_u8 && weight_packed && out && (sel || !train), "%s: NULL tensor", who);
+  S2A_CHECK_ARG(((uintptr_t)image_u8 % 4) == 0 && ((uintptr_t)weight_packed % 16) == 0 && ((uintptr_t)out % 16) == 0 &&
+                ((uintptr_t)bias % 2) == 0 && ((uintptr_t)sel % 8) == 0, "%s: misaligned tensor", who);
+  const StemGeom q = stem_geom(batch, height, width);
+  S2A_CHECK_ARG(q.tiles < (1ll << 31), "%s: too many tiles", who);
+  auto kern = train ? k_stem<true> : k_stem<false>;
+  S2A_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kStemLds));
+  // persistent grid: two workgroups fit a CU (LDS)
+  const unsigned grid = (unsigned)std::min<int64_t>(q.tiles, 256 * 2);
+  kern<<<grid, 256, kStemLds, as_stream(stream)>>>((const uint8_t*)image_u8, (const _Float16*)weight_packed,
+                                                    (const _Float16*)bias, (_Float16*)out, q.H, q.W, q.Hc, q.Wc, q.Hp,
+                                                    q.Wp, q.tiles_x, q.tiles_y, divisor, (int)q.tiles, (uint8_t*)sel);
+  S2A_LAUNCH_CHECK();
+  return S2A_OK;
+}
+}  // namespace
+
 extern "C" int s2a_stem_u8_f16(const void* image_u8, const void* weight_packed, const void* bias, void* out,
                                int64_t batch, int64_t height, int64_t width, float divisor,
                                s2a_stream_t stream) {
-  S2A_CHECK_ARG(batch >= 0 && height >= 7 && width >= 7, "stem: bad shape");
-  S2A_CHECK_ARG(width % 4 == 0, "stem: image width must be a multiple of 4 (aligned 32-bit loads of RGB rows)");
-  S2A_CHECK_ARG(divisor > 0, "stem: divisor must be positive");
-  S2A_CHECK_ARG(batch * height * width * 3 < (1ll << 40), "stem: image too large");
-  if (batch == 0) return S2A_OK;
-  S2A_CHECK_ARG(image_u8 && weight_packed && out, "stem: NULL tensor");
-  S2A_CHECK_ARG(((uintptr_t)image_u8 % 4) == 0 && ((uintptr_t)weight_packed % 16) == 0 && ((uintptr_t)out % 16) == 0 &&
-                ((uintptr_t)bias % 2) == 0, "stem: misaligned tensor");
-  const int H = (int)height, W = (int)width;
-  const int Hc = (H - 1) / 2 + 1, Wc = (W - 1) / 2 + 1;        // 7x7 / 2 / pad 3
-  const int Hp = (Hc - 1) / 2 + 1, Wp = (Wc - 1) / 2 + 1;      // 3x3 / 2 / pad 1
-  const int tiles_x = (Wp + 7) / 8, tiles_y = (Hp + 7) / 8;
-  const int64_t tiles = batch * tiles_x * tiles_y;
-  S2A_CHECK_ARG(tiles < (1ll << 31), "stem: too many tiles");
-  auto kern = k_stem;
-  S2A_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kStemLds));
-  // persistent grid: two workgroups fit a CU (LDS)
-  const unsigned grid = (unsigned)std::min<int64_t>(tiles, 256 * 2);
-  kern<<<grid, 256, kStemLds, as_stream(stream)>>>((const uint8_t*)image_u8, (const _Float16*)weight_packed,
-                                                    (const _Float16*)bias, (_Float16*)out, H, W, Hc, Wc, Hp,
-                                                    Wp, tiles_x, tiles_y, divisor, (int)tiles);
+  return stem_forward("stem", false, image_u8, weight_packed, bias, out, nullptr, batch, height, width, divisor, stream);
+}
+
+extern "C" int s2a_stem_u8_f16_train(const void* image_u8, const void* weight_packed, const void* bias, void* out, void* sel,
+                                     int64_t batch, int64_t height, int64_t width, float divisor, s2a_stream_t stream) {
+  return stem_forward("stem_train", true, image_u8, weight_packed, bias, out, sel, batch, height, width, divisor, stream);
+}
+
+extern "C" int s2a_stem_backward_slices(int64_t batch, int64_t height, int64_t width) {
+  if (stem_shape_problem(batch, height, width) || batch == 0) return 0;
+  const StemGeom q = stem_geom(batch, height, width);
+  if (q.tiles >= (1ll << 31)) return 0;
+  return (int)std::min<int64_t>(q.tiles, kBwdMaxSlices);      // (shapes only)
+}
+
+extern "C" int s2a_stem_backward_f16(const void* image_u8, const void* out, const void* sel, const void* grad_out,
+                                     void* partial, int slices, int64_t batch, int64_t height, int64_t width,
+                                     float divisor, s2a_stream_t stream) {
+  const char* problem = stem_shape_problem(batch, height, width);
+  S2A_CHECK_ARG(!problem, "stem_backward: %s", problem);
+  S2A_CHECK_ARG(batch > 0, "stem_backward: bad shape (an empty batch has no slices)");
+  S2A_CHECK_ARG(divisor > 0, "stem_backward: divisor must be positive");
+  const StemGeom q = stem_geom(batch, height, width);
+  S2A_CHECK_ARG(q.tiles < (1ll << 31), "stem_backward: too many tiles");
+  const int want = s2a_stem_backward_slices(batch, height, width);
+  S2A_CHECK_ARG(slices == want, "stem_backward: slices is %d, s2a_stem_backward_slices answers %d", slices, want);
+  S2A_CHECK_ARG(image_u8 && out && sel && grad_out && partial, "stem_backward: NULL tensor");
+  S2A_CHECK_ARG(((uintptr_t)image_u8 % 4) == 0 && aligned16(out) && aligned16(sel) && aligned16(grad_out) && aligned16(partial),
+                "stem_backward: misaligned tensor (the image 4 bytes, everything else 16)");
+  k_stem_bwd<<<(unsigned)slices, 256, 0, as_stream(stream)>>>((const uint8_t*)image_u8, (const _Float16*)out,
+                                                              (const uint8_t*)sel, (const _Float16*)grad_out, (float*)partial,
+                                                              q.H, q.W, q.Hp, q.Wp, q.tiles_x, q.tiles_y, divisor, (int)q.tiles);
   S2A_LAUNCH_CHECK();
   return S2A_OK;
 }

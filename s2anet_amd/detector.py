@@ -127,19 +127,34 @@ class DetectorBackbone(nn.Module):
         return tuple(outs)
 
     def forward(self, x):
+        """x: the normalised float batch; or, with own_grad_entry on the stem conv (train_kernels(entry=True)) and grad
+        enabled, the raw uint8 batch: the stem then trains on the own kernels (StemU8Function, / 255 inside) when the shapes
+        allow (stem_limits), and on the stock route from x.to(dtype) / 255 when they do not"""
         assert 0 not in self.out_indices
+        conv = self.backbone[0][0]
+        if x.dtype == torch.uint8 and getattr(conv, "own_grad_entry", False) and torch.is_grad_enabled():
+            if self.stem_limits(x) and conv.weight.dtype in (torch.float16, torch.float32) and conv.weight.is_cuda and \
+                    (conv.bias is None or conv.bias.dtype == conv.weight.dtype):
+                from .fused import StemU8Function
+                return self._stages(StemU8Function.apply(x, conv.weight, conv.bias, 255.0))
+            x = x.to(conv.weight.dtype) / 255
         return self._stages(self.backbone[1][0](self.backbone[0](x)))
+
+    def stem_limits(self, imgs_u8):
+        """what the fused stem kernels need, either way: the BN-folded 7x7 / s2 / p3 conv with its ReLU, the 3x3 / s2 / p1
+        pool, a uint8 channels-last RGB batch on the GPU, at least 7 pixels a side, the width a multiple of 4"""
+        conv, pool = self.backbone[0][0], self.backbone[1][0]
+        return (isinstance(conv, FusedConv2d) and conv.fuse_relu and
+                tuple(conv.weight.shape) == (64, 3, 7, 7) and conv.stride == (2, 2) and conv.padding == (3, 3) and
+                isinstance(pool, nn.MaxPool2d) and pool.kernel_size == 3 and pool.stride == 2 and pool.padding == 1 and
+                not pool.ceil_mode and imgs_u8.is_cuda and imgs_u8.dtype == torch.uint8 and imgs_u8.dim() == 4 and
+                imgs_u8.shape[1] == 3 and imgs_u8.shape[3] % 4 == 0 and min(imgs_u8.shape[2:]) >= 7 and
+                imgs_u8.permute(0, 2, 3, 1).is_contiguous())
 
     def stem_fusable(self, imgs_u8):
         """uint8 channels-last batch + BN-folded stem: /255, conv1, ReLU and the max-pool run as one kernel"""
-        conv, pool = self.backbone[0][0], self.backbone[1][0]
-        return (isinstance(conv, FusedConv2d) and conv.fuse_relu and conv.weight.dtype == torch.float16 and
-                tuple(conv.weight.shape) == (64, 3, 7, 7) and conv.stride == (2, 2) and conv.padding == (3, 3) and
-                isinstance(pool, nn.MaxPool2d) and pool.kernel_size == 3 and pool.stride == 2 and pool.padding == 1 and
-                not pool.ceil_mode and imgs_u8.is_cuda and imgs_u8.dtype == torch.uint8 and imgs_u8.shape[1] == 3 and
-                imgs_u8.shape[3] % 4 == 0 and min(imgs_u8.shape[2:]) >= 7 and
-                imgs_u8.permute(0, 2, 3, 1).is_contiguous() and not torch.is_grad_enabled() and
-                not os.environ.get("S2A_NO_FUSED_STEM"))
+        return (self.stem_limits(imgs_u8) and self.backbone[0][0].weight.dtype == torch.float16 and
+                not torch.is_grad_enabled() and not os.environ.get("S2A_NO_FUSED_STEM"))
 
     def forward_u8(self, imgs_u8, divisor=255.0):
         """forward() on the raw uint8 batch with the fused stem (s2a_stem_u8_f16)"""
@@ -200,10 +215,27 @@ class FPN(nn.Module):
                 dst.copy_(prev)
         return buf
 
-    def forward(self, inputs):
-        lat = [l(inputs[i]) for i, l in enumerate(self.lateral_convs)]
+    def _laterals_entry(self, inputs):
+        """the laterals and the top-down sums with own_grad_entry (train_kernels(entry=True)): a step inside train_up2_ok is
+        one FusedConvUp2Function, every other step the stock line of forward()"""
+        from .fused import FusedConvUp2Function, train_up2_ok
+        lat = [None] * self.num_ins
+        lat[-1] = self.lateral_convs[-1](inputs[-1])
         for i in range(self.num_ins - 1, 0, -1):
-            lat[i - 1] = lat[i - 1] + F.interpolate(lat[i], scale_factor=2, mode="nearest")
+            l, x = self.lateral_convs[i - 1], inputs[i - 1]
+            if getattr(l, "own_grad_entry", False) and train_up2_ok(x, l, lat[i]):
+                lat[i - 1] = FusedConvUp2Function.apply(x, l.weight, l.bias, lat[i])
+            else:
+                lat[i - 1] = l(x) + F.interpolate(lat[i], scale_factor=2, mode="nearest")
+        return lat
+
+    def forward(self, inputs):
+        if any(getattr(l, "own_grad_entry", False) for l in self.lateral_convs):
+            lat = self._laterals_entry(inputs)
+        else:
+            lat = [l(inputs[i]) for i, l in enumerate(self.lateral_convs)]
+            for i in range(self.num_ins - 1, 0, -1):
+                lat[i - 1] = lat[i - 1] + F.interpolate(lat[i], scale_factor=2, mode="nearest")
         outs = [self.fpn_convs[i](lat[i]) for i in range(self.num_ins)]
         for i in range(self.num_outs - self.num_ins):
             outs.append(self.fpn_convs[self.num_ins + i](inputs[-1] if i == 0 else outs[-1]))

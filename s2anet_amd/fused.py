@@ -436,13 +436,16 @@ def padded_train_conv(x, weight, bias, relu, Cp, Op):
     return out if Op == O else out[:, :O]
 
 
-def train_kernels(module, enabled=True, strided=False):
+def train_kernels(module, enabled=True, strided=False, entry=False):
     """own_grad = enabled on every FusedConv2d of the tree -> how many were set.  With own_grad a grad-enabled forward of
     an eligible layer (train_conv_ok) runs FusedConvFunction: forward, input gradient, weight gradient, bias gradient and
     ReLU mask on the project's kernels.  Every other layer and every other call keeps its route.
     strided=True: a second opt-in, own_grad_strided = enabled on the same modules (not set or cleared otherwise) -- the
     stride-2 layers (train_conv_strided_ok: the 3x3 / s2 conv2 and the 1x1 / s2 downsample of a stage's first bottleneck,
     FPN's two extra levels) run FusedConvS2Function under grad.  The return value is the same count.
+    entry=True: the third opt-in, own_grad_entry = enabled on the same modules (not set or cleared otherwise) -- the stem
+    trains from the uint8 batch (DetectorBackbone.forward: StemU8Function, the 7x7 convolution, its ReLU and the max-pool
+    in one launch each way) and FPN's top-down steps run FusedConvUp2Function (FPN.forward).  The same count again.
     In deterministic mode (s2anet_amd.deterministic) own_grad also takes the layers that fail train_conv_ok for their width
     alone (train_pad_widths) and, set here as well but not counted, the ORConv2d modules of the tree."""
     from .orn import ORConv2d
@@ -452,6 +455,8 @@ def train_kernels(module, enabled=True, strided=False):
             m.own_grad = bool(enabled)
             if strided:
                 m.own_grad_strided = bool(enabled)
+            if entry:
+                m.own_grad_entry = bool(enabled)
             n += 1
         elif isinstance(m, ORConv2d):
             m.own_grad = bool(enabled)
@@ -573,8 +578,68 @@ class FusedConvS2Function(torch.autograd.Function):
         return gx, gw, gb, (g if need_r else None), None
 
 
+def train_up2_ok(x, conv, coarse):
+    """limits of FusedConvUp2Function, and nothing but limits: a 1x1 lateral inside train_conv_ok, a coarser level of
+    exactly half the size in f16 channels-last with the lateral's output width, and something that requires grad"""
+    return (train_conv_ok(x, conv) and tuple(conv.kernel_size) == (1, 1) and coarse.is_cuda and coarse.dtype == torch.float16 and
+            coarse.dim() == 4 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and
+            tuple(coarse.shape) == (x.shape[0], conv.out_channels, x.shape[2] // 2, x.shape[3] // 2) and
+            coarse.is_contiguous(memory_format=torch.channels_last) and _needs_grad(x, conv.weight, conv.bias, coarse))
+
+
+class FusedConvUp2Function(torch.autograd.Function):
+    """FPN's top-down step conv1x1(x) + bias + nearest-2x-upsample(coarse) with its backward on the own kernels: the forward
+    is s2a_conv1x1_add_up2_f16 on the forward filter of s2a_conv_pack_weight_train (packed on every call, as in
+    FusedConvFunction); backward: grad_x by s2a_conv_nhwc_f16 on the input-gradient filter, grad_weight by
+    s2a_conv_backward_weight_f16, grad_bias by the prep pass, grad_coarse by s2a_sum_pool2x2_f16 (the four fine gradients of a
+    coarse pixel summed over f32 in a fixed order, one rounding).  Only what needs_input_grad asks for is computed.  No host
+    read, no float atomic, no memset node: capturable, and bit-equal from run to run."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, coarse):
+        O, C = weight.shape[:2]
+        L = _lib.lib()
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        w = weight.detach()
+        w = w if w.is_contiguous() else w.contiguous()
+        fwd = torch.empty((w.numel(),), dtype=torch.float16, device=x.device)
+        dgrad = torch.empty_like(fwd) if need_x else None
+        with torch.cuda.device(x.device):
+            _lib.check(L.s2a_conv_pack_weight_train(_lib.ptr(w), _lib.dtype_code(w), O, C, 1, _lib.ptr(fwd), _lib.ptr(dgrad),
+                                                    _lib.stream_ptr(x.device)))
+        b = None if bias is None else bias.detach().to(torch.float16).contiguous()
+        out = conv1x1_add_up2(x, fwd, b, coarse.detach(), O)
+        ctx.save_for_backward(x if need_w else None, dgrad)
+        ctx.geom = (tuple(x.shape), O, 1, weight.dtype, None if bias is None else bias.dtype)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, dgrad = ctx.saved_tensors
+        (B, C, H, W), O, _, wdtype, _ = ctx.geom
+        need_x, need_w, _, need_c = ctx.needs_input_grad[:4]
+        L, dev = _lib.lib(), grad_out.device
+        gx = gw = gc = None
+        with torch.cuda.device(dev):
+            g, gb = _train_prep(ctx, grad_out, None, B * H * W)          # (no ReLU: g is grad_out, dense f16 channels-last)
+            if need_x:
+                gx = conv_f16(g, dgrad, None, C, 1, 1, False)
+            if need_w:
+                gw = torch.empty((O, C, 1, 1), dtype=wdtype, device=dev)
+                ws = torch.empty((L.s2a_conv_backward_weight_f16_workspace_bytes(B, C, H, W, O, 1),), dtype=torch.uint8, device=dev)
+                _lib.check(L.s2a_conv_backward_weight_f16(_lib.ptr(x), _lib.ptr(g), _lib.ptr(gw), _lib.dtype_code(gw), B, C, H, W,
+                                                          O, 1, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+            if need_c:
+                gc = torch.empty((B, O, H // 2, W // 2), dtype=torch.float16, device=dev, memory_format=torch.channels_last)
+                _lib.check(L.s2a_sum_pool2x2_f16(_lib.ptr(g), _lib.ptr(gc), B, H, W, O, _lib.stream_ptr(dev)))
+        return gx, gw, gb, gc
+
+
 class FusedConv2d(nn.Conv2d):
     """nn.Conv2d + (bias, optional residual, optional ReLU) epilogue in one pass"""
+    own_grad_entry = False      # train_kernels(entry=True): the stem conv trains from the uint8 batch (StemU8Function), FPN's
+    #                             laterals run their top-down step as FusedConvUp2Function
     own_grad = False        # train_kernels(): grad-enabled forwards of eligible layers (train_conv_ok) run FusedConvFunction
     own_grad_strided = False    # train_kernels(strided=True): those of the stride-2 layers (train_conv_strided_ok) run
     #                             FusedConvS2Function
@@ -688,3 +753,68 @@ def stem_u8(imgs_u8, packed_weight, bias, divisor=255.0):
         _lib.check(_lib.lib().s2a_stem_u8_f16(_lib.ptr(imgs_u8), _lib.ptr(packed_weight), _lib.ptr(b), _lib.ptr(out),
                                               B, H, W, float(divisor), _lib.stream_ptr(imgs_u8.device)))
     return out
+
+
+STEM_GRAD_COLS = 64 * 147 + 64      # floats per slice of s2a_stem_backward_f16: the filter gradient, then the bias sums
+
+
+def stem_out_hw(H, W):
+    """pooled size of the stem: 7x7 / 2 / pad 3, then 3x3 / 2 / pad 1"""
+    Hc, Wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    return (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1
+
+
+class StemU8Function(torch.autograd.Function):
+    """StemU8Function.apply(imgs_u8, weight, bias, divisor): relu(conv7x7/2(img / divisor) + bias) -> maxpool 3x3/2 from the
+    uint8 batch [B,3,H,W] (channels-last storage), [B,64,H/4,W/4] f16 channels-last, with the backward on the own kernels.
+    weight [64,3,7,7] / bias [64] or None: f16 parameters or f32 masters (rounded to f16 on the way in, gradients in the
+    master dtype straight from the f32 sums).  The filter is packed on every call, never cached (as FusedConvFunction).
+    Forward s2a_stem_u8_f16_train: the inference kernel's bits for finite parameters, torch's ReLU and pool for non-finite
+    ones, plus one byte per output naming the pooled tap.  Saved: imgs_u8, out and those bytes -- no normalised image, no
+    [B,64,H/2,W/2] activation, no int64 indices.  Backward s2a_stem_backward_f16 + s2a_conv_backward_weight_s2_reduce: the
+    filter and bias gradient (an image gets none), per-slice f32 sums added in slice order.  No host read, no float atomic,
+    no memset node, geometry from shapes only: capturable, and bit-equal from run to run."""
+
+    @staticmethod
+    def forward(ctx, imgs_u8, weight, bias, divisor):
+        _lib.require_cuda(imgs_u8, weight, bias)
+        B, C, H, W = imgs_u8.shape
+        assert C == 3 and imgs_u8.dtype == torch.uint8 and imgs_u8.permute(0, 2, 3, 1).is_contiguous()
+        assert tuple(weight.shape) == (64, 3, 7, 7) and weight.dtype in (torch.float16, torch.float32)
+        assert bias is None or (bias.dtype == weight.dtype and tuple(bias.shape) == (64,))
+        dev = imgs_u8.device
+        Hp, Wp = stem_out_hw(H, W)
+        packed = stem_pack_weight(weight)
+        b = None if bias is None else bias.detach().to(torch.float16).contiguous()
+        out = torch.empty((B, 64, Hp, Wp), dtype=torch.float16, device=dev, memory_format=torch.channels_last)
+        sel = torch.empty((B, Hp, Wp, 64), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().s2a_stem_u8_f16_train(_lib.ptr(imgs_u8), _lib.ptr(packed), _lib.ptr(b), _lib.ptr(out), _lib.ptr(sel),
+                                                        B, H, W, float(divisor), _lib.stream_ptr(dev)))
+        ctx.save_for_backward(imgs_u8, out, sel)
+        ctx.geom = (B, H, W, float(divisor), weight.dtype, bias is not None)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        imgs_u8, out, sel = ctx.saved_tensors
+        B, H, W, divisor, wdtype, has_bias = ctx.geom
+        need_w, need_b = ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
+        if not (need_w or need_b):
+            return None, None, None, None
+        L, dev = _lib.lib(), grad_out.device
+        go = grad_out if grad_out.dtype == torch.float16 else grad_out.to(torch.float16)
+        go = go.contiguous(memory_format=torch.channels_last)
+        with torch.cuda.device(dev):
+            st = _lib.stream_ptr(dev)
+            slices = L.s2a_stem_backward_slices(B, H, W)
+            partial = torch.empty((slices, STEM_GRAD_COLS), dtype=torch.float32, device=dev)
+            _lib.check(L.s2a_stem_backward_f16(_lib.ptr(imgs_u8), _lib.ptr(out), _lib.ptr(sel), _lib.ptr(go), _lib.ptr(partial), slices,
+                                               B, H, W, divisor, st))
+            grads = torch.empty((STEM_GRAD_COLS,), dtype=wdtype, device=dev)
+            _lib.check(L.s2a_conv_backward_weight_s2_reduce(_lib.ptr(partial), slices, STEM_GRAD_COLS, _lib.ptr(grads),
+                                                            _lib.dtype_code(grads), st))
+        gw = grads[:64 * 147].view(64, 3, 7, 7) if need_w else None
+        gb = grads[64 * 147:] if need_b else None
+        return None, gw, gb, None
