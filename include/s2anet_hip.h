@@ -975,6 +975,51 @@ typedef struct s2a_train_update_args {
 size_t s2a_train_update_workspace_bytes(int64_t n_trained_chunks);
 int s2a_train_update(const s2a_train_update_args* args, void* workspace, size_t workspace_bytes, s2a_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Training augmentation: the two augmentations the reference's S2ANet recipe enables (data/hyps/hyp.scratch.s2anet.yaml:
+ * degrees 180, fliplr 0.5; flipud is built too, everything else in that file is 0) on a batch of square S x S chips and
+ * its polygon labels (augment_ops.hip).  HSV jitter, mosaic, mixup, free-angle and scaled warps, non-square chips and
+ * letterboxing are not built.
+ *
+ * params int32 [batch, 4] on the device = (rot, flipud, fliplr, 0) per image; rot 0..3 = the reference's angles 0, 90,
+ * -180, -90 degrees.  s2a_augment_draw fills it; a caller may also write it.
+ *
+ * Image (utils/augmentations.py:93-175 with scale = shear = translate = perspective = 0, then np.flipud, np.fliplr of
+ * utils/datasets_rotation.py:480-492).  The turn M = T R C is an integer pixel map about S / 2, not (S - 1) / 2:
+ *   rot 1: x' = y, y' = S - x      rot 2: x' = S - x, y' = S - y      rot 3: x' = S - y, y' = x      rot 0: untouched
+ * so one source row or column leaves the chip and the facing destination row or column takes the border value 114:
+ * row 0 at rot 1, row 0 and column 0 at rot 2, column 0 at rot 3.  The flips are plain reversals after the turn (a border
+ * line moves with them).  cv2.warpAffine is OpenCV and is restated from its definition for these integer maps.
+ *
+ * Labels: f32 [n_rows, 10] = (image, class, x1, y1 .. x4, y4) in pixels, rows in any order; an image outside [0, batch)
+ * marks padding.  In float64: the points go through M; the row is dropped unless the centre of the minimum-area
+ * rectangle of the points truncated towards zero lies in [0, S] x [0, S] (box_candidates_rotation_filter_center); flipud
+ * is y <- S - y, fliplr x <- S - x (S, not S - 1: the reference's); the points are truncated again and their
+ * minimum-area rectangle becomes (cx, cy, w, h, theta), w the long side and theta its direction atan2(dy, dx) in image
+ * coordinates in [-pi/4, 3pi/4) (poly_to_rotated_box_np; what s2a_rbox_to_poly inverts).  Row g of targets f32
+ * [n_rows, 7] = (image, class, cx, cy, w, h, theta); no compaction.  A padding row, a dropped row and a row whose
+ * truncated points span no area get image = -1 and zeros (OpenCV gives the last kind a zero-area box that matches no
+ * anchor: a deviation).  normalize != 0 divides cx, w by the width and cy, h by the height (xywhtheta2xywhtheta_n).
+ * Coordinates beyond +-2^29 saturate.  cv2.minAreaRect is restated as the smallest of the edge-aligned bounding
+ * rectangles of the convex hull.  status int64 [4] on the device = (rows that are not padding, kept, dropped by the
+ * centre filter, dropped as degenerate).
+ *
+ * Draw: Philox4x32-10 with counter (image, 0, step_lo, step_hi) and key (seed_lo, seed_hi); rot = word 0 & 3 when
+ * turn != 0, else 0; flipud = u1 < p_flipud, fliplr = u2 < p_fliplr with u = (word >> 8) * 2^-24 from words 1 and 2.
+ * step and seed are int64 device scalars; the launch reads step and then adds 1 to it, so every replay of a captured
+ * graph draws afresh.
+ *
+ * All three launch on `stream`, take no workspace, allocate nothing and read nothing back.  S2A_EINVAL before any HIP call
+ * for: NULL pointers, sizes that are not positive, height != width, a width that is no multiple of 4 (images: below 8),
+ * probabilities outside [0, 1], src and dst that overlap, misaligned buffers (images 4 bytes, params 16, step / seed /
+ * status 8).  src and dst are uint8 channels-last [batch, height, width, 3]. */
+int s2a_augment_draw(int64_t* step, const int64_t* seed, int64_t batch, int turn, float p_flipud, float p_fliplr,
+                     int32_t* params, s2a_stream_t stream);
+int s2a_augment_images_u8(const uint8_t* src, const int32_t* params, int64_t batch, int64_t height, int64_t width,
+                          uint8_t* dst, s2a_stream_t stream);
+int s2a_augment_labels(const float* labels, int64_t n_rows, const int32_t* params, int64_t batch, int64_t height,
+                       int64_t width, int normalize, float* targets, int64_t* status, s2a_stream_t stream);
+
 /* 0 for a normal build; non-zero when an object was compiled with a measurement / ablation switch (-DS2A_MEASURE,
  * -DS2A_WABL=..., -DS2A_STAMP=1: such a build may skip work or print diagnostics).  Bits 0-7 (the former AlignConv
  * ablation mask) are no longer set by any object. */

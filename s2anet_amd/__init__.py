@@ -19,6 +19,7 @@ from .scene import tile_grid, chip_names, gather_chips, merge_detections, SceneD
 from .evaluate import evaluate_task1, Task1Evaluator, Task1Result, claim_tp_fp
 from .optim import TrainUpdate, reference_param_groups, reference_lr
 from .fp8 import quantize_weight_e4m3, calibrate_fp8, fp8_towers
+from .augment import TrainAugment
 
 __all__ = [
     "box_iou_rotated", "nms_rotated", "ml_nms_rotated", "multiclass_nms_rotated",
@@ -31,5 +32,5 @@ __all__ = [
     "TrainUpdate", "reference_param_groups", "reference_lr",
     "train_kernels", "train_conv_ok", "train_conv_strided_ok", "FusedConv2d", "FusedConvFunction",
     "StemU8Function", "FusedConvUp2Function", "train_up2_ok",
-    "quantize_weight_e4m3", "calibrate_fp8", "fp8_towers", "deterministic",
+    "quantize_weight_e4m3", "calibrate_fp8", "fp8_towers", "deterministic", "TrainAugment",
 ]

@@ -227,6 +227,9 @@ SYMBOLS = {
                        [ctypes.POINTER(EvalCurves), c_vp, c_sz, c_vp]),
     "s2a_train_update_workspace_bytes": (c_sz, [c_i64]),
     "s2a_train_update": (c_int, [ctypes.POINTER(TrainUpdateArgs), c_vp, c_sz, c_vp]),
+    "s2a_augment_draw": (c_int, [c_vp, c_vp, c_i64, c_int, c_f32, c_f32, c_vp, c_vp]),
+    "s2a_augment_images_u8": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
+    "s2a_augment_labels": (c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp]),
     "s2a_delta2bbox_rotated": (c_int, [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp]),
     "s2a_fam_refine_anchors": (c_int, [c_vp, c_i64, c_i64, c_i64, c_f32, c_f32, c_int, c_int,
                                        c_vp, c_vp]),
