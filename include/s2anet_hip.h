@@ -522,6 +522,12 @@ int s2a_conv_pack_weight_f16(const void* weight, int64_t out_channels, int64_t c
 int s2a_conv_nhwc_f16(const void* x, const void* weight_frag, const void* bias, const void* residual,
                       void* out, int64_t batch, int64_t channels, int64_t height, int64_t width,
                       int64_t out_channels, int ksize, int stride, int relu, s2a_stream_t stream);
+/* the k_conv_f16<TAPS, OG, PH, SD, TAIL, HT> that s2a_conv_nhwc_f16 would launch for these sizes now (the tile-shape
+   switches are read from the environment as the call reads them) -> form[6].  No HIP call, no device needed.
+   S2A_EINVAL with the entry point's own text for sizes it refuses (a call with a residual also refuses an output of
+   2^31 bytes or more; the query takes no residual and answers as a call without one).  batch 0: the form of the sizes. */
+int s2a_conv_nhwc_f16_form(int64_t batch, int64_t channels, int64_t height, int64_t width,
+                           int64_t out_channels, int ksize, int stride, int32_t form[6]);
 
 /* Training side of the regular convolutions above (FusedConv2d with own_grad; stride 1, ksize 3 / pad 1 or ksize 1 / pad 0,
  * C and O multiples of 64, every tensor under 2^31 bytes).  All three are fixed launch sequences without host reads, float

@@ -155,6 +155,7 @@ SYMBOLS = {
     "s2a_conv_pack_weight_f16": (c_int, [c_vp, c_i64, c_i64, c_int, c_vp, c_vp]),
     "s2a_conv_nhwc_f16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_int,
                                   c_int, c_vp]),
+    "s2a_conv_nhwc_f16_form": (c_int, [c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_int, ctypes.POINTER(ctypes.c_int32)]),
     "s2a_conv_pack_weight_train": (c_int, [c_vp, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp]),
     "s2a_conv_backward_prep_f16_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "s2a_conv_backward_prep_f16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_i64, c_i64, c_vp, c_sz, c_vp]),

@@ -1261,7 +1261,15 @@ int launch_conv(const _Float16* x, const _Float16* wfrag, const _Float16* bias, 
   return S2A_OK;
 }
 
-// the arguments of one launch_conv call: an entry point fills them once and picks the kernel form with run<...>()
+// the template arguments of k_conv_f16 as a value: what the conv_form_*() functions decide and ConvCall::run(form) launches
+struct ConvForm {
+  int taps, og, ph, sd, tail, ht;
+  bool operator==(const ConvForm& o) const {
+    return taps == o.taps && og == o.og && ph == o.ph && sd == o.sd && tail == o.tail && ht == o.ht;
+  }
+};
+
+// the arguments of one launch_conv call: an entry point fills them once and hands the form it decided to run(form)
 struct ConvCall {
   const _Float16 *x, *wfrag, *bias, *residual;
   _Float16* out;
@@ -1277,13 +1285,112 @@ struct ConvCall {
     return launch_conv<TAPS, OG, PH, SD, TAIL, HT>(x, wfrag, bias, residual, out, B, C, H, W, Ho, Wo, cstride, O, relu, st, levels,
                                                    level_tiles, res_up, ex);
   }
+  // THE list of the k_conv_f16 instantiations this file builds; a form outside it is refused in front of any launch
+  int run(const ConvForm& f) const {
+#define S2A_CONV_FORM(TAPS, OG, PH, SD, TAIL, HT) \
+  if (f == ConvForm{TAPS, OG, PH, SD, TAIL, HT}) return run<TAPS, OG, PH, SD, TAIL, HT>()
+    S2A_CONV_FORM(9, 4, 1, 2, 0, 0);   // 3x3 stride 2
+    S2A_CONV_FORM(9, 2, 1, 2, 0, 0);
+    S2A_CONV_FORM(9, 2, 2, 1, 0, 0);   // 3x3 on 16 x 16 tiles, the filter through LDS
+    S2A_CONV_FORM(9, 1, 2, 1, 0, 0);
+    S2A_CONV_FORM(9, 4, 2, 1, 0, 0);
+    S2A_CONV_FORM(9, 4, 1, 1, 0, 1);   // 3x3 on 4 x 16 tiles
+    S2A_CONV_FORM(9, 2, 1, 1, 0, 1);
+    S2A_CONV_FORM(9, 4, 1, 1, 0, 0);   // 3x3 on 8 x 16 tiles
+    S2A_CONV_FORM(9, 2, 1, 1, 0, 0);
+    S2A_CONV_FORM(9, 1, 1, 1, 0, 0);
+    S2A_CONV_FORM(1, 4, 1, 2, 0, 0);   // 1x1 on 64 positions
+    S2A_CONV_FORM(1, 4, 1, 1, 0, 0);   // 1x1 on 128 positions
+    S2A_CONV_FORM(1, 2, 1, 1, 0, 0);
+    S2A_CONV_FORM(1, 1, 1, 1, 0, 0);
+    S2A_CONV_FORM(9, 1, 2, 1, 1, 0);   // 3x3 + the bottleneck's 1x1 tail, 16 x 16 and 8 x 16 tiles
+    S2A_CONV_FORM(9, 1, 1, 1, 1, 0);
+#undef S2A_CONV_FORM
+    s2a::set_error("conv: no kernel of form <%d, %d, %d, %d, %d, %d>", f.taps, f.og, f.ph, f.sd, f.tail, f.ht);
+    return S2A_EINVAL;
+  }
 };
-}  // namespace
-}  // namespace s2a
 
-extern "C" int s2a_conv_nhwc_f16(const void* x, const void* weight_frag, const void* bias, const void* residual,
-                                 void* out, int64_t batch, int64_t channels, int64_t height, int64_t width,
-                                 int64_t out_channels, int ksize, int stride, int relu, s2a_stream_t stream) {
+// ---- which form a call launches: host arithmetic and getenv only.  The tile-shape switches are A/B switches for
+// measurements and tests, which flip them between calls of one process: the environment is read on every call.
+// S2A_CONV_PH, S2A_CONV_PH_NARROW = 1|2: any set value other than 2 is 1
+inline int env_ph(const char* name, int ph) {
+  const char* f = getenv(name);
+  return f ? (atoi(f) == 2 ? 2 : 1) : ph;
+}
+// S2A_CONV3_HALF, S2A_CONV1_HALF = 0|1
+inline bool env_flag(const char* name, bool on) {
+  const char* f = getenv(name);
+  return f ? atoi(f) != 0 : on;
+}
+inline int conv_og(int64_t out_channels) { return out_channels % 256 == 0 ? 4 : (out_channels % 128 == 0 ? 2 : 1); }
+
+// s2a_conv_nhwc_f16 (and its query s2a_conv_nhwc_f16_form), for sizes that conv_nhwc_check_sizes lets through
+ConvForm conv_form_nhwc(int64_t batch, int64_t channels, int64_t height, int64_t width, int64_t out_channels, int ksize,
+                        int stride) {
+  const int64_t Ho = (height - 1) / stride + 1, Wo = (width - 1) / stride + 1;   // k=1,p=0 / k=3,p=1 (s = 1, 2)
+  const int og = conv_og(out_channels);
+  const int64_t groups = (out_channels + 64 * og - 1) / (64 * og);
+  if (ksize == 3 && stride == 2) return {9, og == 4 ? 4 : 2, 1, 2, 0, 0};
+  if (ksize == 3 && og < 4 && channels % 64 == 0) {
+    // narrow 3x3 layers (the 64- and 128-map conv2 of the trunk's first stages): the four waves of an 8 x 16 tile
+    // re-load the same filter fragments (4x / 2x the bytes into the CU); 16 x 16 tiles with the filter of each tap
+    // staged once per workgroup through LDS when there are enough tiles to fill the chip.  S2A_CONV_PH_NARROW=1|2
+    const int64_t tiles16 = batch * ((Wo + 15) / 16) * ((Ho + 15) / 16) * groups;
+    if (env_ph("S2A_CONV_PH_NARROW", tiles16 >= 256 ? 2 : 1) == 2) return {9, og, 2, 1, 0, 0};
+  }
+  if (ksize == 3 && og == 4 && channels % 64 == 0) {
+    // large maps (FPN's 3x3 on P3: 128^2 at batch 8): 16 x 16 tiles with the filter through LDS, as the pyramid-packed
+    // towers -- when they still fill the chip twice.  S2A_CONV_PH=1|2
+    const int64_t tiles16 = batch * ((Wo + 15) / 16) * ((Ho + 15) / 16) * groups;
+    if (env_ph("S2A_CONV_PH", tiles16 >= 512 ? 2 : 1) == 2) return {9, 4, 2, 1, 0, 0};
+  }
+  if (ksize == 3 && og >= 2) {
+    // small maps (32^2 at batch 8): fewer 8 x 16 workgroups than CUs -> 4 x 16 tiles (512 -> 512 on 32^2: 54 -> 44 us,
+    // 256 -> 256 on 32^2: 28 -> 19 us; once every CU has a workgroup the smaller tile loses: 256 -> 256 on 64^2
+    // 39.5 -> 43 us).  S2A_CONV3_HALF=0|1
+    const int64_t wgs128 = batch * ((Wo + 15) / 16) * ((Ho + 7) / 8) * groups;
+    if (env_flag("S2A_CONV3_HALF", wgs128 < 256)) return {9, og, 1, 1, 0, 1};
+  }
+  if (ksize == 3) return {9, og, 1, 1, 0, 0};
+  if (og == 4) {
+    // small maps (64^2 / 32^2 at batch 8): 128-position tiles give at most one workgroup per CU, and one workgroup's
+    // chunk pipeline is latency-bound (32 MFMAs per wave between two memory round trips) -- 64-position tiles fill
+    // the chip (2048 -> 512 and 2048 -> 256 on 32^2: 35 -> 26 us, 34 -> 23 us; no gain once every CU has a workgroup).  (ConvCfg<1, 4, 1, 2>: SD = 2 selects the 64-position tile; the spatial
+    // stride of a 1x1 is the cstride argument.)  S2A_CONV1_HALF=0|1
+    const int64_t wgs128 = (batch * Ho * Wo + 127) / 128 * groups;
+    // measured: a win only while the 128-position grid leaves CUs empty
+    if (env_flag("S2A_CONV1_HALF", wgs128 < 256)) return {1, 4, 1, 2, 0, 0};
+  }
+  return {1, og, 1, 1, 0, 0};
+}
+
+// s2a_conv1x1_add_up2_f16: the 128-position 1x1 of the width
+ConvForm conv_form_up2(int64_t out_channels) { return {1, conv_og(out_channels), 1, 1, 0, 0}; }
+
+// the pyramid-packed 3x3 launches (conv3x3_pyramid_impl); has_head: a 1x1 prediction head is fused on the tile
+ConvForm conv_form_pyramid(int64_t channels, int64_t out_channels, bool has_head) {
+  int og = conv_og(out_channels);
+  // A/B switch for measurements; not for the fused 1x1 head, which needs the whole channel range in one workgroup (OG = 4)
+  const char* og_env = getenv("S2A_CONV_OG");
+  if (og_env && !has_head) og = std::min(og, std::max(1, atoi(og_env)));
+  if (og == 3) og = 1;   // (there is no three-group kernel: capped at 3, a 256-map layer runs one group per workgroup)
+  // Full-width towers: 16 x 16 tiles on 512-thread workgroups with the filter staged once per workgroup through
+  // LDS (ConvCfg::kWLds) -- 4-7 % faster than two 8 x 16 workgroups per CU, bit-identical.  S2A_CONV_PH=1|2: A/B switch.
+  // Only the OG = 4 form has 16-row tiles: the level table must be built for the tile height that is launched.
+  const int ph = (og == 4 && channels % 64 == 0) ? env_ph("S2A_CONV_PH", 2) : 1;
+  return {9, og, ph, 1, 0, 0};
+}
+
+// s2a_conv3x3_tail1x1_f16: 16 x 16 tiles when they fill the chip, as the narrow 3x3 layers.  S2A_CONV_PH_NARROW=1|2
+ConvForm conv_form_tail(int64_t batch, int64_t height, int64_t width) {
+  const int64_t tiles16 = batch * ((width + 15) / 16) * ((height + 15) / 16);
+  return {9, 1, env_ph("S2A_CONV_PH_NARROW", tiles16 >= 256 ? 2 : 1), 1, 1, 0};
+}
+
+// the checks of s2a_conv_nhwc_f16 that read sizes only, shared with its query
+int conv_nhwc_check_sizes(int64_t batch, int64_t channels, int64_t height, int64_t width, int64_t out_channels, int ksize,
+                          int stride, bool has_residual) {
   S2A_CHECK_ARG(batch >= 0 && channels > 0 && out_channels > 0 && height > 0 && width > 0, "conv: bad shape");
   S2A_CHECK_ARG(ksize == 3 || ksize == 1, "conv: kernel size must be 1 or 3");
   S2A_CHECK_ARG(stride == 1 || stride == 2, "conv: stride must be 1 or 2");
@@ -1293,65 +1400,37 @@ extern "C" int s2a_conv_nhwc_f16(const void* x, const void* weight_frag, const v
   const uint64_t x_bytes = (uint64_t)batch * height * width * channels * 2;
   S2A_CHECK_ARG(x_bytes < (1ull << 31) && (ksize == 1 || (height < 32000 && width < 32000)),
                 "conv: input too large for 32-bit offsets");
-  S2A_CHECK_ARG(!residual || (uint64_t)batch * ((height - 1) / stride + 1) * ((width - 1) / stride + 1) * out_channels * 2 < (1ull << 31),
+  S2A_CHECK_ARG(!has_residual || (uint64_t)batch * ((height - 1) / stride + 1) * ((width - 1) / stride + 1) * out_channels * 2 < (1ull << 31),
                 "conv: output too large for the fused residual (32-bit offsets)");
+  return S2A_OK;
+}
+}  // namespace
+}  // namespace s2a
+
+// the query: the entry point's own size checks and the conv_form_nhwc call it dispatches on.  (Only a call with a residual
+// bounds the output's size; the query takes none, as a call without one.)
+extern "C" int s2a_conv_nhwc_f16_form(int64_t batch, int64_t channels, int64_t height, int64_t width, int64_t out_channels,
+                                      int ksize, int stride, int32_t form[6]) {
+  if (int rc = conv_nhwc_check_sizes(batch, channels, height, width, out_channels, ksize, stride, false)) return rc;
+  S2A_CHECK_ARG(form, "conv_form: NULL form");
+  const ConvForm f = conv_form_nhwc(batch, channels, height, width, out_channels, ksize, stride);
+  form[0] = f.taps, form[1] = f.og, form[2] = f.ph, form[3] = f.sd, form[4] = f.tail, form[5] = f.ht;
+  return S2A_OK;
+}
+
+extern "C" int s2a_conv_nhwc_f16(const void* x, const void* weight_frag, const void* bias, const void* residual,
+                                 void* out, int64_t batch, int64_t channels, int64_t height, int64_t width,
+                                 int64_t out_channels, int ksize, int stride, int relu, s2a_stream_t stream) {
+  if (int rc = conv_nhwc_check_sizes(batch, channels, height, width, out_channels, ksize, stride, residual != nullptr)) return rc;
   if (batch == 0) return S2A_OK;
   S2A_CHECK_ARG(x && weight_frag && out, "conv: NULL tensor");
   S2A_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)weight_frag % 16) == 0 &&
                 ((uintptr_t)bias % 8) == 0 && ((uintptr_t)residual % 16) == 0, "conv: tensors must be 16-byte aligned");
-  hipStream_t st = as_stream(stream);
   const int Ho = (int)((height - 1) / stride + 1), Wo = (int)((width - 1) / stride + 1);   // k=1,p=0 / k=3,p=1 (s = 1, 2)
-  const int og = out_channels % 256 == 0 ? 4 : (out_channels % 128 == 0 ? 2 : 1);
   const ConvCall c{(const _Float16*)x, (const _Float16*)weight_frag, (const _Float16*)bias, (const _Float16*)residual,
-                   (_Float16*)out, batch, (int)channels, (int)height, (int)width, Ho, Wo, stride, (int)out_channels, relu, st};
-  if (ksize == 3 && stride == 2) {
-    if (og == 4) return c.run<9, 4, 1, 2>();
-    return c.run<9, 2, 1, 2>();
-  }
-  if (ksize == 3 && og < 4 && channels % 64 == 0) {
-    // narrow 3x3 layers (the 64- and 128-map conv2 of the trunk's first stages): the four waves of an 8 x 16 tile
-    // re-load the same filter fragments (4x / 2x the bytes into the CU); 16 x 16 tiles with the filter of each tap
-    // staged once per workgroup through LDS when there are enough tiles to fill the chip.  S2A_CONV_PH_NARROW=1|2
-    const int64_t tiles16 = batch * ((Wo + 15) / 16) * ((Ho + 15) / 16) * ((out_channels + 64 * og - 1) / (64 * og));
-    int ph = tiles16 >= 256 ? 2 : 1;
-    if (const char* f = getenv("S2A_CONV_PH_NARROW")) ph = atoi(f) == 2 ? 2 : 1;
-    if (ph == 2) {
-      if (og == 2) return c.run<9, 2, 2>();
-      return c.run<9, 1, 2>();
-    }
-  }
-  if (ksize == 3 && og == 4 && channels % 64 == 0) {
-    // large maps (FPN's 3x3 on P3: 128^2 at batch 8): 16 x 16 tiles with the filter through LDS, as the pyramid-packed
-    // towers -- when they still fill the chip twice.  S2A_CONV_PH=1|2
-    const int64_t tiles16 = batch * ((Wo + 15) / 16) * ((Ho + 15) / 16) * (out_channels / 256);
-    int ph = tiles16 >= 512 ? 2 : 1;
-    if (const char* f = getenv("S2A_CONV_PH")) ph = atoi(f) == 2 ? 2 : 1;
-    if (ph == 2) return c.run<9, 4, 2>();
-  }
-  if (ksize == 3 && og >= 2) {
-    // small maps (32^2 at batch 8): fewer 8 x 16 workgroups than CUs -> 4 x 16 tiles (512 -> 512 on 32^2: 54 -> 44 us,
-    // 256 -> 256 on 32^2: 28 -> 19 us; once every CU has a workgroup the smaller tile loses: 256 -> 256 on 64^2
-    // 39.5 -> 43 us).  S2A_CONV3_HALF=0|1
-    const int64_t wgs128 = batch * ((Wo + 15) / 16) * ((Ho + 7) / 8) * ((out_channels + 64 * og - 1) / (64 * og));
-    bool half = wgs128 < 256;
-    if (const char* f = getenv("S2A_CONV3_HALF")) half = atoi(f) != 0;
-    if (half) {
-      if (og == 4) return c.run<9, 4, 1, 1, false, 1>();
-      return c.run<9, 2, 1, 1, false, 1>();
-    }
-  }
-  if (ksize == 3) return og == 4 ? c.run<9, 4>() : (og == 2 ? c.run<9, 2>() : c.run<9, 1>());
-  if (og == 4) {
-    // small maps (64^2 / 32^2 at batch 8): 128-position tiles give at most one workgroup per CU, and one workgroup's
-    // chunk pipeline is latency-bound (32 MFMAs per wave between two memory round trips) -- 64-position tiles fill
-    // the chip (2048 -> 512 and 2048 -> 256 on 32^2: 35 -> 26 us, 34 -> 23 us; no gain once every CU has a workgroup).  (ConvCfg<1, 4, 1, 2>: SD = 2 selects the 64-position tile; the spatial
-    // stride of a 1x1 is the cstride argument.)  S2A_CONV1_HALF=0|1
-    const int64_t wgs128 = ((int64_t)batch * Ho * Wo + 127) / 128 * (out_channels / 256);
-    bool half = wgs128 < 256;   // measured: a win only while the 128-position grid leaves CUs empty
-    if (const char* f = getenv("S2A_CONV1_HALF")) half = atoi(f) != 0;
-    if (half) return c.run<1, 4, 1, 2>();
-  }
-  return og == 4 ? c.run<1, 4>() : (og == 2 ? c.run<1, 2>() : c.run<1, 1>());
+                   (_Float16*)out, batch, (int)channels, (int)height, (int)width, Ho, Wo, stride, (int)out_channels, relu,
+                   as_stream(stream)};
+  return c.run(conv_form_nhwc(batch, channels, height, width, out_channels, ksize, stride));
 }
 
 extern "C" int s2a_conv3x3_tail1x1_f16(const void* x, const void* weight_frag, const void* bias,
@@ -1385,12 +1464,9 @@ extern "C" int s2a_conv3x3_tail1x1_f16(const void* x, const void* weight_frag, c
     ex.chain_out = (_Float16*)chain_out;
     ex.chain_O = (int)chain_channels;
   }
-  int ph = batch * ((width + 15) / 16) * ((height + 15) / 16) >= 256 ? 2 : 1;
-  if (const char* f = getenv("S2A_CONV_PH_NARROW")) ph = atoi(f) == 2 ? 2 : 1;
   const ConvCall c{(const _Float16*)x, (const _Float16*)weight_frag, (const _Float16*)bias, nullptr, (_Float16*)out, batch, 64,
                    (int)height, (int)width, (int)height, (int)width, 1, 64, 1, as_stream(stream), nullptr, 0, 0, ex};
-  if (ph == 2) return c.run<9, 1, 2, 1, true>();
-  return c.run<9, 1, 1, 1, true>();
+  return c.run(conv_form_tail(batch, height, width));
 }
 
 namespace s2a {
@@ -1452,12 +1528,10 @@ extern "C" int s2a_conv1x1_add_up2_f16(const void* x, const void* weight_frag, c
   S2A_CHECK_ARG(x && weight_frag && coarse && out, "conv_add_up2: NULL tensor");
   S2A_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)weight_frag % 16) == 0 &&
                 ((uintptr_t)bias % 2) == 0 && ((uintptr_t)coarse % 16) == 0, "conv_add_up2: tensors must be 16-byte aligned");
-  hipStream_t st = as_stream(stream);
-  const int og = out_channels % 256 == 0 ? 4 : (out_channels % 128 == 0 ? 2 : 1);
   const ConvCall c{(const _Float16*)x, (const _Float16*)weight_frag, (const _Float16*)bias, (const _Float16*)coarse,
-                   (_Float16*)out, batch, (int)channels, (int)height, (int)width, (int)height, (int)width, 1, (int)out_channels, 0, st,
-                   nullptr, 0, 1};
-  return og == 4 ? c.run<1, 4>() : (og == 2 ? c.run<1, 2>() : c.run<1, 1>());
+                   (_Float16*)out, batch, (int)channels, (int)height, (int)width, (int)height, (int)width, 1, (int)out_channels, 0,
+                   as_stream(stream), nullptr, 0, 1};
+  return c.run(conv_form_up2(out_channels));
 }
 
 extern "C" int s2a_conv_pack_weight_f16(const void* weight, int64_t out_channels, int64_t channels, int ksize,
@@ -1519,16 +1593,8 @@ static int conv3x3_pyramid_impl(const void* x, const void* weight_frag, const vo
   S2A_CHECK_ARG((channels % 64 == 0 || channels == 32) && out_channels % 64 == 0,
                 "conv_pyramid: channels must be 32 or a multiple of 64, out_channels a multiple of 64");
   LevelTab lt; int64_t pix = 0;
-  int og = out_channels % 256 == 0 ? 4 : (out_channels % 128 == 0 ? 2 : 1);
-  // A/B switch for measurements; not for the fused 1x1 head, which needs the whole channel range in one workgroup (OG = 4)
-  const char* og_env = getenv("S2A_CONV_OG");
-  if (og_env && !ex.head_w) og = std::min(og, std::max(1, atoi(og_env)));
-  // Full-width towers: 16 x 16 tiles on 512-thread workgroups with the filter staged once per workgroup through
-  // LDS (ConvCfg::kWLds) -- 4-7 % faster than two 8 x 16 workgroups per CU, bit-identical.  S2A_CONV_PH=1|2: A/B switch.
-  // Only the OG = 4 form has 16-row tiles: the level table must be built for the tile height that is launched.
-  int ph = (og == 4 && channels % 64 == 0) ? 2 : 1;
-  if (const char* f = getenv("S2A_CONV_PH")) ph = atoi(f) == 2 && og == 4 && channels % 64 == 0 ? 2 : 1;
-  const int64_t tiles = build_levels(pyr, batch, &lt, &pix, 8 * ph);
+  const ConvForm form = conv_form_pyramid(channels, out_channels, ex.head_w != nullptr);
+  const int64_t tiles = build_levels(pyr, batch, &lt, &pix, 8 * form.ph);
   S2A_CHECK_ARG(tiles >= 0, "conv_pyramid: bad level table (1..8 levels, positive sizes)");
   S2A_CHECK_ARG((uint64_t)pix * channels * 2 < (1ull << 31), "conv_pyramid: input too large for 32-bit offsets");
   if (batch == 0) return S2A_OK;
@@ -1536,12 +1602,10 @@ static int conv3x3_pyramid_impl(const void* x, const void* weight_frag, const vo
   S2A_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)weight_frag % 16) == 0 &&
                 ((uintptr_t)bias % 8) == 0 && ((uintptr_t)residual % 16) == 0, "conv_pyramid: tensors must be 16-byte aligned");
   if (lt.n == 1) lt.n = 2, lt.tile0[1] = 0x7fffffff;   // keep the rebind path (n > 1) for a one-level table
-  hipStream_t st = as_stream(stream);
   const ConvCall c{(const _Float16*)x, (const _Float16*)weight_frag, (const _Float16*)bias, (const _Float16*)residual,
-                   (_Float16*)out, batch, (int)channels, lt.H[0], lt.W[0], lt.H[0], lt.W[0], 1, (int)out_channels, relu, st,
-                   &lt, tiles, 0, ex};
-  if (ph == 2 && og == 4) return c.run<9, 4, 2>();
-  return og == 4 ? c.run<9, 4>() : (og == 2 ? c.run<9, 2>() : c.run<9, 1>());
+                   (_Float16*)out, batch, (int)channels, lt.H[0], lt.W[0], lt.H[0], lt.W[0], 1, (int)out_channels, relu,
+                   as_stream(stream), &lt, tiles, 0, ex};
+  return c.run(form);
 }
 
 extern "C" int s2a_conv3x3_narrow_pyramid_f16(const void* x, const void* weight_frag, const void* bias, void* out,

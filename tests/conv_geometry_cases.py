@@ -4,7 +4,8 @@ tests/test_gpu_conv_geometry.py (which holds every instantiation of k_conv_f16, 
 trunk forms to the float64 reference of oracle/conv64.py).
 
 A case fixes all four tile-shape switches, so the instantiation it runs is a function of (ksize, stride, C, O, switches)
-alone: route() below, read off s2a_conv_nhwc_f16.  The geometries are the smallest at which each mechanism of a tile
+alone: route() below, the tests' own statement of the dispatch, which tests/test_conv_geometry_cpu.py holds to the library's
+answer (s2a_conv_nhwc_f16_form), the default thresholds included.  The geometries are the smallest at which each mechanism of a tile
 kernel can still go wrong, chosen per instantiation from its tile shape; inputs are drawn on the CPU from a generator
 seeded by the case id, so both files see the same numbers.
 
@@ -43,23 +44,37 @@ def og_of(O):
     return 4 if O % 256 == 0 else (2 if O % 128 == 0 else 1)
 
 
-def route(ksize, stride, C, O, sw):
-    """the k_conv_f16<TAPS, OG, PH, SD, false, HT> that s2a_conv_nhwc_f16 launches when all four switches are set
-    -> (TAPS, OG, PH, SD, HT)"""
-    assert set(sw) == set(SWITCHES) and ksize in (1, 3) and stride in (1, 2)
+def route(ksize, stride, C, O, sw, B=None, H=None, W=None):
+    """the k_conv_f16<TAPS, OG, PH, SD, false, HT> that s2a_conv_nhwc_f16 launches -> (TAPS, OG, PH, SD, HT).  A switch
+    absent from sw is decided by the entry point's threshold on the launch's workgroup count, which needs B, H, W:
+    16 x 16 tiles from 256 (OG 1, 2) / 512 (OG 4) workgroups on, 4 x 16 tiles and 64-position 1x1 tiles below 256
+    workgroups of the 8 x 16 / 128-position form"""
+    assert set(sw) <= set(SWITCHES) and ksize in (1, 3) and stride in (1, 2)
     assert (C % 64 == 0 or C == 32) and O % 64 == 0 and not (ksize == 3 and stride == 2 and O % 128)
     og = og_of(O)
+    groups = (O + 64 * og - 1) // (64 * og)
+    Ho, Wo = out_hw(H, W, stride) if set(sw) != set(SWITCHES) else (None, None)
+
+    def tiles(rows):
+        return B * ((Wo + 15) // 16) * ((Ho + rows - 1) // rows) * groups
+
+    def tall(name, least):
+        return sw[name] == "2" if name in sw else tiles(16) >= least
+
+    def half(name, wgs):
+        return int(sw[name]) != 0 if name in sw else wgs() < 256
+
     if ksize == 3 and stride == 2:
         return (9, 4 if og == 4 else 2, 1, 2, 0)
     if ksize == 3:
-        if og < 4 and C % 64 == 0 and sw["S2A_CONV_PH_NARROW"] == "2":
+        if og < 4 and C % 64 == 0 and tall("S2A_CONV_PH_NARROW", 256):
             return (9, og, 2, 1, 0)
-        if og == 4 and C % 64 == 0 and sw["S2A_CONV_PH"] == "2":
+        if og == 4 and C % 64 == 0 and tall("S2A_CONV_PH", 512):
             return (9, 4, 2, 1, 0)
-        if og >= 2 and int(sw["S2A_CONV3_HALF"]) != 0:
+        if og >= 2 and half("S2A_CONV3_HALF", lambda: tiles(8)):
             return (9, og, 1, 1, 1)
         return (9, og, 1, 1, 0)
-    if og == 4 and int(sw["S2A_CONV1_HALF"]) != 0:
+    if og == 4 and half("S2A_CONV1_HALF", lambda: (B * Ho * Wo + 127) // 128 * groups):
         return (1, 4, 1, 2, 0)            # (SD = 2 selects the 64-position tile of a 1x1; its stride is cstride)
     return (1, og, 1, 1, 0)
 

@@ -1,6 +1,8 @@
 """The dense-convolution case table (tests/conv_geometry_cases.py) checked without a GPU: the float64 reference against
-torch's own float64 convolution, the bound against an emulation of the kernel's arithmetic, what the table reaches, and
-the shapes the entry point refuses."""
+torch's own float64 convolution, the bound against an emulation of the kernel's arithmetic, what the table reaches, the
+shapes the entry point refuses, and route() -- the table's statement of which instantiation a call launches -- against the
+library's own answer (s2a_conv_nhwc_f16_form): with the switches of every case, with none at the default thresholds, and
+over the values a switch can be set to."""
 import ctypes
 
 import pytest
@@ -138,6 +140,159 @@ def test_guarded_views_are_aligned_and_banded():
     assert not o.all_written() and o.bands_untouched()
     o.buf[o.hi] = 0
     assert not o.bands_untouched()
+
+
+# ----------------------------------------------------------------------------- the library's own answer
+def _query(B, C, H, W, O, k, s):
+    """s2a_conv_nhwc_f16_form -> (return code, (TAPS, OG, PH, SD, HT), TAIL)"""
+    from s2anet_amd import _lib
+    f = (ctypes.c_int32 * 6)(*([-1] * 6))
+    rc = _lib.lib().s2a_conv_nhwc_f16_form(B, C, H, W, O, k, s, f)
+    return rc, (f[0], f[1], f[2], f[3], f[5]), f[4]
+
+
+def _set_switches(monkeypatch, sw):
+    for name in G.SWITCHES:
+        if name in sw:
+            monkeypatch.setenv(name, sw[name])
+        else:
+            monkeypatch.delenv(name, raising=False)
+
+
+def test_query_answers_the_instantiation_of_every_case(monkeypatch):
+    """(a) with a case's switches set, the library routes it to the instantiation the table says it runs"""
+    for c in G.CASES:
+        _set_switches(monkeypatch, c["sw"])
+        assert _query(c["B"], c["C"], c["H"], c["W"], c["O"], c["k"], c["s"]) == (0, c["inst"], 0), c["id"]
+    print("query against the table: %d cases" % len(G.CASES))
+
+
+# geometries (B, H, W) on both sides of each default threshold, with what is counted there at stride 1:
+#   16 x 16 tiles, O = 64 / 128 (from 256 on: filter through LDS): 240 | 256, B = 3: 255 | 258
+#   16 x 16 tiles, O = 256 (from 512 on): 511 | 512, B = 3: 510 | 513
+#   8 x 16 workgroups, O = 128 / 256 (below 256: 4 x 16 tiles): 255 | 256, B = 3: 255 | 258
+#   128-position workgroups of a 1x1, O = 256 (below 256: 64 positions): 255 | 256, B = 3: 255 | 258; the last pair at stride 2
+#   and two maps far below every threshold
+THRESHOLD_GEOMS = {
+    "tiles16_256": ((1, 240, 256), (1, 241, 256), (3, 80, 272), (3, 32, 688)),
+    "tiles16_512": ((1, 112, 1168), (1, 256, 512), (3, 160, 272), (3, 144, 304)),
+    "wgs8x16_256": ((1, 120, 272), (1, 128, 256), (3, 40, 272), (3, 16, 688)),
+    "wgs128_256": ((1, 255, 128), (1, 256, 128), (3, 85, 128), (3, 86, 128), (1, 510, 256), (1, 512, 256)),
+    "small": ((1, 8, 16), (1, 1, 1)),
+}
+GRID_CHANNELS, GRID_OUT = (32, 64, 192), (64, 128, 256, 512)
+
+
+def test_threshold_geometries_sit_on_both_sides():
+    def count(g, rows):
+        B, H, W = g
+        return B * ((W + 15) // 16) * ((H + rows - 1) // rows)
+    T = THRESHOLD_GEOMS
+    assert [count(g, 16) for g in T["tiles16_256"]] == [240, 256, 255, 258]
+    assert [count(g, 16) for g in T["tiles16_512"]] == [511, 512, 510, 513]
+    assert [count(g, 8) for g in T["wgs8x16_256"]] == [255, 256, 255, 258]
+    assert max(count(g, 16) for g in T["wgs8x16_256"]) < 256          # (the 16 x 16 rules stay out of the way)
+    assert [(B * H * W + 127) // 128 for B, H, W in T["wgs128_256"][:4]] == [255, 256, 255, 258]
+    assert [(B * ((H - 1) // 2 + 1) * ((W - 1) // 2 + 1) + 127) // 128 for B, H, W in T["wgs128_256"][4:]] == [255, 256]
+    for gs in T.values():
+        for B, H, W in gs:
+            assert B * H * W * max(GRID_CHANNELS) * 2 < 2 ** 31 and B * H * W * max(GRID_OUT) * 2 < 2 ** 31 and max(H, W) < 32000
+
+
+def test_default_routes_equal_the_query(monkeypatch):
+    """(b) no switch set: route()'s four thresholds against the library over ksize x stride x C x O x the geometries
+    above (3x3 at stride 2 with O = 64 is refused and left to the refusal test).  Default routing reaches all fourteen
+    instantiations: none needs a switch."""
+    _set_switches(monkeypatch, {})
+    reached, points = set(), 0
+    for k in (1, 3):
+        for s in (1, 2):
+            for C in GRID_CHANNELS:
+                for O in GRID_OUT:
+                    if k == 3 and s == 2 and O % 128:
+                        continue
+                    for gs in THRESHOLD_GEOMS.values():
+                        for B, H, W in gs:
+                            want = G.route(k, s, C, O, {}, B, H, W)
+                            assert _query(B, C, H, W, O, k, s) == (0, want, 0), (k, s, C, O, B, H, W)
+                            reached.add(want)
+                            points += 1
+    assert reached == set(G.ALL_INSTANTIATIONS) and len(reached) == 14
+    # each threshold decides between the two forms it is there for, at the sizes it was set for
+    T = THRESHOLD_GEOMS
+    for below, above in (T["tiles16_256"][:2], T["tiles16_256"][2:]):
+        assert G.route(3, 1, 64, 64, {}, *below) == (9, 1, 1, 1, 0) and G.route(3, 1, 64, 64, {}, *above) == (9, 1, 2, 1, 0)
+        assert G.route(3, 1, 64, 128, {}, *below) == (9, 2, 1, 1, 0) and G.route(3, 1, 64, 128, {}, *above) == (9, 2, 2, 1, 0)
+    for below, above in (T["tiles16_512"][:2], T["tiles16_512"][2:]):
+        assert G.route(3, 1, 64, 256, {}, *below) == (9, 4, 1, 1, 0) and G.route(3, 1, 64, 256, {}, *above) == (9, 4, 2, 1, 0)
+    for below, above in (T["wgs8x16_256"][:2], T["wgs8x16_256"][2:]):
+        for O, og in ((128, 2), (256, 4)):
+            assert G.route(3, 1, 64, O, {}, *below) == (9, og, 1, 1, 1) and G.route(3, 1, 64, O, {}, *above) == (9, og, 1, 1, 0)
+    for s, (below, above) in ((1, T["wgs128_256"][:2]), (1, T["wgs128_256"][2:4]), (2, T["wgs128_256"][4:])):
+        assert G.route(1, s, 64, 256, {}, *below) == (1, 4, 1, 2, 0) and G.route(1, s, 64, 256, {}, *above) == (1, 4, 1, 1, 0)
+    print("default routes: %d points" % points)
+
+
+def _atoi(v):
+    """the C library's atoi on the values used below"""
+    import re
+    m = re.match(r"\s*[+-]?\d+", v)
+    return int(m.group(0)) if m else 0
+
+
+def test_switch_values_are_parsed_as_documented(monkeypatch):
+    """(c) S2A_CONV_PH, S2A_CONV_PH_NARROW: a set value is 2 when atoi gives 2 and 1 otherwise, the empty string included;
+    S2A_CONV3_HALF, S2A_CONV1_HALF: on when atoi gives non-zero.  Each at a shape below and one above its threshold, where
+    the two settings launch different forms."""
+    T = THRESHOLD_GEOMS
+    shapes = {"S2A_CONV_PH_NARROW": (3, 1, 64, 128, T["tiles16_256"][:2]), "S2A_CONV_PH": (3, 1, 64, 256, T["tiles16_512"][:2]),
+              "S2A_CONV3_HALF": (3, 1, 64, 256, T["wgs8x16_256"][:2]), "S2A_CONV1_HALF": (1, 1, 64, 256, T["wgs128_256"][:2])}
+    points = 0
+    for name, (k, s, C, O, geoms) in shapes.items():
+        for B, H, W in geoms:
+            seen = set()
+            for v in ("", "0", "1", "2", "3", "x"):
+                if name in ("S2A_CONV_PH", "S2A_CONV_PH_NARROW"):
+                    meant = "2" if _atoi(v) == 2 else "1"
+                else:
+                    meant = "1" if _atoi(v) != 0 else "0"
+                _set_switches(monkeypatch, {name: v})
+                want = G.route(k, s, C, O, {name: meant}, B, H, W)
+                assert _query(B, C, H, W, O, k, s) == (0, want, 0), (name, v, B, H, W)
+                seen.add(want)
+                points += 1
+            assert len(seen) == 2, (name, seen)
+    print("switch values: %d points" % points)
+
+
+def test_query_refuses_what_the_call_refuses(monkeypatch):
+    """(d) the sizes the entry point refuses are refused by the query with the same code and text; an empty batch is
+    answered with the form of the sizes; the bound on the output of a fused residual is the call's alone"""
+    from s2anet_amd import _lib
+    L = _lib.lib()
+    _set_switches(monkeypatch, {})
+    z, one = ctypes.c_void_p(0), ctypes.c_void_p(16)
+    #          B, C, H, W, O, k, s
+    refused = ((1, 64, 8, 8, 96, 3, 1, "multiple of 64"), (1, 64, 8, 8, 64, 3, 2, "stride 2"), (1, 64, 8, 8, 192, 3, 2, "stride 2"),
+               (1, 48, 8, 8, 64, 3, 1, "multiple of 64"), (1, 64, 8, 8, 64, 5, 1, "kernel size"), (1, 64, 8, 8, 64, 3, 3, "stride"),
+               (1, 64, 0, 8, 64, 3, 1, "bad shape"), (-1, 64, 8, 8, 64, 3, 1, "bad shape"),
+               (1, 64, 4096, 4096, 64, 1, 1, "32-bit offsets"), (1, 64, 1, 32000, 64, 3, 1, "32-bit offsets"))
+    for *sizes, text in refused:
+        B, C, H, W, O, k, s = sizes
+        assert L.s2a_conv_nhwc_f16(one, one, one, z, one, B, C, H, W, O, k, s, 1, z) == _lib.EINVAL
+        said = L.s2a_last_error().decode()
+        assert text in said, (sizes, said)
+        rc, form, tail = _query(*sizes)
+        assert rc == _lib.EINVAL and L.s2a_last_error().decode() == said, (sizes, said)
+        assert form == (-1,) * 5 and tail == -1                       # nothing written
+    assert _query(0, 64, 8, 8, 256, 3, 1) == (0, G.route(3, 1, 64, 256, {}, 0, 8, 8), 0)
+    assert _query(1, 64, 1, 32000, 64, 1, 1)[0] == 0                  # (a 1x1 has no limit on the map's side)
+    # 64 -> 512 on 2048 x 1024: x is 256 MiB, the output 2 GiB.  Only a call with a residual refuses it; the query, as a
+    # call without one (which gets as far as its NULL tensor), answers
+    big = (1, 64, 2048, 1024, 512, 1, 1)
+    assert L.s2a_conv_nhwc_f16(one, one, one, one, one, *big, 1, z) == _lib.EINVAL and "fused residual" in L.s2a_last_error().decode()
+    assert L.s2a_conv_nhwc_f16(z, one, one, z, one, *big, 1, z) == _lib.EINVAL and "NULL tensor" in L.s2a_last_error().decode()
+    assert _query(*big) == (0, G.route(1, 1, 64, 512, {}, 1, 2048, 1024), 0)
 
 
 def test_refused_shapes_come_back_as_argument_errors():

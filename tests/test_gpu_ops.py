@@ -1113,7 +1113,11 @@ def test_own_conv3x3_stride2_vs_torch():
 
 def test_narrow_conv3x3_filter_through_lds_matches(monkeypatch):
     """64- and 128-map 3x3 layers on 16 x 16 tiles with the filter staged through LDS (S2A_CONV_PH_NARROW=2) are
-    bit-identical to the 8 x 16 form, ragged sizes included; same for the fused bottleneck tail"""
+    bit-identical to what S2A_CONV_PH_NARROW=1 launches, ragged sizes included; same for the fused bottleneck tail.
+    What the two settings launch with the other switches unset (s2a_conv_nhwc_f16_form): the two 64-map shapes compare
+    the 8 x 16 <9,1> with <9,1,2>; the two 128-map shapes have 15 and 4 workgroups of 8 x 16, far below 256, so they
+    compare the 4 x 16 <9,2,1,1,false,1> with <9,2,2>, not the 8 x 16 <9,2>
+    (test_gpu_conv_geometry.py::test_3x3_tile_shapes_give_equal_bits compares all three)"""
     from s2anet_amd.fused import FusedConv2d, bottleneck_tail, conv_f16, conv_pack_weight
     g = torch.Generator().manual_seed(5)
     for (B, C, H, W, O) in ((2, 64, 40, 56, 64), (1, 128, 33, 47, 128), (2, 64, 16, 16, 128), (1, 192, 20, 20, 64)):
