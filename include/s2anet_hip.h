@@ -1026,6 +1026,53 @@ int s2a_augment_images_u8(const uint8_t* src, const int32_t* params, int64_t bat
 int s2a_augment_labels(const float* labels, int64_t n_rows, const int32_t* params, int64_t batch, int64_t height,
                        int64_t width, int normalize, float* targets, int64_t* status, s2a_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Training-mode BatchNorm (bn_ops.hip; the slice plan and the moment merges are csrc/bn_plan.hpp).  Reference:
+ * torch.nn.BatchNorm2d in training mode as used in models/backbone.py:54-83 (the bottleneck's bn1 / bn2 / bn3 and the
+ * downsample's norm): batch statistics over (N, H, W), gamma / beta, running statistics moved by `momentum` with the
+ * unbiased variance.
+ *
+ * All four passes work on an f16 channels-last activation seen as [positions, channels], positions = B H W >= 2,
+ * channels % 64 == 0, under 2^31 bytes.  Each is one walk over memory with 16-byte accesses; a lane keeps its channel
+ * octet, and lanes, then slices are combined in a fixed order: no float atomics, no memset node, no host read, grid and
+ * slice count from (positions, channels) only -- capturable, and the same bits every run.
+ *
+ * s2a_bn_slices: the slice count of a problem (0 for a refused one).  `partial` is a caller's f32 buffer
+ * [slices][2][channels] that the launch writes completely: per-slice (mean, M2) for the statistics, per-slice
+ * (sum g, sum g xhat) for the backward.  There is no opaque workspace.
+ *
+ * s2a_bn_train_stats_f16: mean f32 [C] and invstd = 1 / sqrt(biased var + eps) f32 [C].  Lanes accumulate shifted sums in
+ * f32, the merges (lanes, then slices) run in double: |mean| >> std costs no accuracy.  running_mean / running_var (both
+ * or neither; f32 or f16 by running_dtype) are updated in place: (1 - momentum) r + momentum batch, the variance
+ * unbiased by positions / (positions - 1).
+ *
+ * s2a_bn_train_apply_f16: out = relu?((x - mean) invstd weight + bias (+ residual)), one rounding to f16.  weight / bias
+ * f32 or f16 (param_dtype).  The ReLU keeps a NaN (torch's), unlike the fused ReLU of the inference launches.
+ *
+ * s2a_bn_backward_reduce_f16: g = out <= 0 ? 0 : grad_out when `out` is given (a NaN output passes the gradient), else
+ * g = grad_out.  With `partial`: grad_bias = sum g and grad_weight = sum g xhat (either may be NULL; param_dtype; from the
+ * f32 slice sums added in a fixed order, one rounding) and coef f32 [2][C] = (sum g / P, sum g xhat / P).  With `g`: the
+ * masked gradient is also written there (it is the residual's gradient); needs `out`.  partial == NULL: the mask alone.
+ *
+ * s2a_bn_backward_input_f16: grad_input = weight invstd (g - coef[0] - xhat coef[1]); with `out` given, `g` is grad_out
+ * and the mask is applied again here.
+ *
+ * S2A_EINVAL before any HIP call: NULL or misaligned pointers (activations and partial 16 bytes, vectors 4), channels
+ * that are no multiple of 64, positions < 2, 2^31 bytes or more, a slice count other than s2a_bn_slices answers. */
+int s2a_bn_slices(int64_t positions, int64_t channels);
+int s2a_bn_train_stats_f16(const void* x, int64_t positions, int64_t channels, double eps, double momentum, float* partial,
+                           int slices, float* mean, float* invstd, void* running_mean, void* running_var, int running_dtype,
+                           s2a_stream_t stream);
+int s2a_bn_train_apply_f16(const void* x, const float* mean, const float* invstd, const void* weight, const void* bias,
+                           int param_dtype, const void* residual, void* out, int64_t positions, int64_t channels, int relu,
+                           s2a_stream_t stream);
+int s2a_bn_backward_reduce_f16(const void* grad_out, const void* x, const void* out, const float* mean, const float* invstd,
+                               void* g, float* partial, int slices, void* grad_weight, void* grad_bias, int param_dtype,
+                               float* coef, int64_t positions, int64_t channels, s2a_stream_t stream);
+int s2a_bn_backward_input_f16(const void* g, const void* x, const void* out, const float* mean, const float* invstd,
+                              const void* weight, int param_dtype, const float* coef, void* grad_input, int64_t positions,
+                              int64_t channels, s2a_stream_t stream);
+
 /* 0 for a normal build; non-zero when an object was compiled with a measurement / ablation switch (-DS2A_MEASURE,
  * -DS2A_WABL=..., -DS2A_STAMP=1: such a build may skip work or print diagnostics).  Bits 0-7 (the former AlignConv
  * ablation mask) are no longer set by any object. */

@@ -20,6 +20,7 @@ from .evaluate import evaluate_task1, Task1Evaluator, Task1Result, claim_tp_fp
 from .optim import TrainUpdate, reference_param_groups, reference_lr
 from .fp8 import quantize_weight_e4m3, calibrate_fp8, fp8_towers
 from .augment import TrainAugment
+from .norm import BatchNormTrainFunction, batch_norm_train, train_bn_ok, train_batchnorm
 
 __all__ = [
     "box_iou_rotated", "nms_rotated", "ml_nms_rotated", "multiclass_nms_rotated",
@@ -33,4 +34,5 @@ __all__ = [
     "train_kernels", "train_conv_ok", "train_conv_strided_ok", "FusedConv2d", "FusedConvFunction",
     "StemU8Function", "FusedConvUp2Function", "train_up2_ok",
     "quantize_weight_e4m3", "calibrate_fp8", "fp8_towers", "deterministic", "TrainAugment",
+    "BatchNormTrainFunction", "batch_norm_train", "train_bn_ok", "train_batchnorm",
 ]

@@ -231,6 +231,13 @@ SYMBOLS = {
     "s2a_augment_draw": (c_int, [c_vp, c_vp, c_i64, c_int, c_f32, c_f32, c_vp, c_vp]),
     "s2a_augment_images_u8": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
     "s2a_augment_labels": (c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp]),
+    "s2a_bn_slices": (c_int, [c_i64, c_i64]),
+    "s2a_bn_train_stats_f16": (c_int, [c_vp, c_i64, c_i64, ctypes.c_double, ctypes.c_double, c_vp, c_int, c_vp, c_vp, c_vp, c_vp,
+                                       c_int, c_vp]),
+    "s2a_bn_train_apply_f16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_i64, c_int, c_vp]),
+    "s2a_bn_backward_reduce_f16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_i64, c_i64,
+                                           c_vp]),
+    "s2a_bn_backward_input_f16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_i64, c_vp]),
     "s2a_delta2bbox_rotated": (c_int, [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp]),
     "s2a_fam_refine_anchors": (c_int, [c_vp, c_i64, c_i64, c_i64, c_f32, c_f32, c_int, c_int,
                                        c_vp, c_vp]),

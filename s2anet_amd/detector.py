@@ -57,7 +57,82 @@ class BottleNeck(nn.Module):
             return self.conv3(self.conv2(out), residual), None  # relu(conv3 + bias + residual) in one pass
         return self._forward_plain(x), None
 
+    own_grad_norm = False       # norm.train_batchnorm(): the fourth opt-in -- a grad-enabled training forward of the unfolded
+    #                             block runs on the own kernels (_forward_own_norm) when every layer passes its predicate
+
+    def _own_norm_layers(self):
+        """(conv, bn) pairs of the unfolded block: conv1, conv2, conv3 and, when there is one, the downsample"""
+        pairs = [(self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)]
+        if self.downsample is not None:
+            pairs.append((self.downsample[0], self.downsample[1]))
+        return pairs
+
+    def _own_norm_ok(self, x):
+        """the four conditions of the own route: the flag, grad enabled, the norms in training mode, every layer inside its
+        predicate.  The predicates are evaluated on x and on empty tensors of the intermediate shapes, once per input geometry
+        and parameter dtype (the answer is cached on the block)"""
+        if not (self.own_grad_norm and torch.is_grad_enabled()):
+            return False
+        pairs = self._own_norm_layers()
+        if not all(type(c) is nn.Conv2d and isinstance(b, nn.BatchNorm2d) and b.training for c, b in pairs):
+            return False
+        if self.downsample is not None and len(self.downsample) != 2:
+            return False
+        key = (tuple(x.shape), x.dtype, x.device, x.is_contiguous(memory_format=torch.channels_last)) + tuple(
+            (c.weight.dtype, c.weight.device, c.bias is None, b.weight is not None and b.weight.dtype,
+             b.running_mean is not None and b.running_mean.dtype, b.running_var is not None and b.running_var.dtype,
+             type(b.momentum), b.affine, b.track_running_stats) for c, b in pairs)
+        cached = self.__dict__.get("_own_norm_cache")
+        if cached is None or cached[0] != key:
+            cached = (key, self._own_norm_predicates(x))
+            self.__dict__["_own_norm_cache"] = cached
+        return cached[1]
+
+    def _own_norm_predicates(self, x):
+        from .fused import train_conv_ok, train_conv_strided_ok
+        from .norm import train_bn_ok
+        if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float16):
+            return False
+
+        def conv_ok(t, conv, bn):
+            """-> an empty tensor of conv's output shape when conv takes t and bn takes that, else None"""
+            strided = tuple(conv.stride) == (2, 2)
+            if conv.bias is not None or not (train_conv_strided_ok if strided else train_conv_ok)(t, conv):
+                return None
+            B, _, H, W = t.shape
+            if strided:
+                H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+            y = torch.empty((B, conv.out_channels, H, W), dtype=torch.float16, device=t.device, memory_format=torch.channels_last)
+            return y if train_bn_ok(y, bn) else None
+
+        y = conv_ok(x, self.conv1, self.bn1)
+        y = conv_ok(y, self.conv2, self.bn2) if y is not None else None
+        y = conv_ok(y, self.conv3, self.bn3) if y is not None else None
+        if y is None:
+            return False
+        r = x if self.downsample is None else conv_ok(x, self.downsample[0], self.downsample[1])
+        return r is not None and train_bn_ok(y, self.bn3, r)
+
+    def _forward_own_norm(self, x):
+        """the unfolded block in training mode on the own kernels: conv1 -> BN + ReLU, conv2 (stride 1 or 2) -> BN + ReLU,
+        conv3 -> BN + residual + ReLU in one apply launch, downsample conv -> BN (models/backbone.py:54-83)"""
+        from .fused import FusedConvFunction, FusedConvS2Function
+        from .norm import batch_norm_train
+
+        def conv(c, t):
+            fn = FusedConvS2Function if tuple(c.stride) == (2, 2) else FusedConvFunction
+            return fn.apply(t, c.weight, None, None, False)
+
+        out = batch_norm_train(conv(self.conv1, x), self.bn1, relu=True)
+        out = batch_norm_train(conv(self.conv2, out), self.bn2, relu=True)
+        residual = x
+        if self.downsample is not None:
+            residual = batch_norm_train(conv(self.downsample[0], x), self.downsample[1])
+        return batch_norm_train(conv(self.conv3, out), self.bn3, residual, relu=True)
+
     def _forward_plain(self, x):
+        if self._own_norm_ok(x):
+            return self._forward_own_norm(x)
         residual = x
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.relu(self.bn2(self.conv2(out)))
@@ -118,6 +193,13 @@ class DetectorBackbone(nn.Module):
     def _stages(self, x):
         """layer1 .. layer4 on the pooled stem output"""
         outs, pre = [], None
+        first = self.backbone[1][1][0]
+        if getattr(first, "own_grad_norm", False) and torch.is_grad_enabled() and x.is_cuda and \
+                isinstance(first.bn1, nn.BatchNorm2d) and first.bn1.training and \
+                not (x.dtype == torch.float16 and x.is_contiguous(memory_format=torch.channels_last)):
+            # trunk entry of the own BatchNorm route (norm.train_batchnorm): the pooled stem output, cast once to f16
+            # channels-last with stock differentiable ops (the stem itself stays on its route)
+            x = x.to(torch.float16).contiguous(memory_format=torch.channels_last)
         for i in range(1, len(self.backbone)):
             seq = self.backbone[i][1] if i == 1 else self.backbone[i]
             after = self.backbone[i + 1][0] if i + 1 < len(self.backbone) else None
