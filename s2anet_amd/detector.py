@@ -69,8 +69,8 @@ class BottleNeck(nn.Module):
 
     def _own_norm_ok(self, x):
         """the four conditions of the own route: the flag, grad enabled, the norms in training mode, every layer inside its
-        predicate.  The predicates are evaluated on x and on empty tensors of the intermediate shapes, once per input geometry
-        and parameter dtype (the answer is cached on the block)"""
+        predicate.  The predicates are evaluated on x, on the shapes that follow from it and on the parameters, once per input
+        geometry and parameter dtype (the answer is cached on the block)"""
         if not (self.own_grad_norm and torch.is_grad_enabled()):
             return False
         pairs = self._own_norm_layers()
@@ -89,29 +89,28 @@ class BottleNeck(nn.Module):
         return cached[1]
 
     def _own_norm_predicates(self, x):
-        from .fused import train_conv_ok, train_conv_strided_ok
-        from .norm import train_bn_ok
-        if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float16):
-            return False
+        """every layer inside its predicate, on shapes: (B, C, H, W) goes through train_shape_problem to (B, O, Ho, Wo) and that
+        through bn_shape_problem; what integers cannot say is asked of x itself and of the parameters.  No tensor is made."""
+        from .fused import train_shape_problem, train_tensors_problem
+        from .norm import bn_layer_problem, bn_shape_problem
 
-        def conv_ok(t, conv, bn):
-            """-> an empty tensor of conv's output shape when conv takes t and bn takes that, else None"""
-            strided = tuple(conv.stride) == (2, 2)
-            if conv.bias is not None or not (train_conv_strided_ok if strided else train_conv_ok)(t, conv):
-                return None
-            B, _, H, W = t.shape
-            if strided:
-                H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-            y = torch.empty((B, conv.out_channels, H, W), dtype=torch.float16, device=t.device, memory_format=torch.channels_last)
-            return y if train_bn_ok(y, bn) else None
+        def conv_bn(shape, conv, bn):
+            """-> the output's shape when conv takes an f16 channels-last activation of `shape` and bn takes the result, else None"""
+            B, C, H, W = shape
+            O, s = conv.out_channels, conv.stride
+            out = (B, O, (H - 1) // s[0] + 1, (W - 1) // s[1] + 1)
+            bad = (conv.bias is not None or C != conv.in_channels or train_tensors_problem(None, conv.weight, None, C) or
+                   train_shape_problem(conv.kernel_size, s, conv.padding, conv.dilation, conv.groups, C, O, B, H, W) or
+                   O != bn.num_features or bn_shape_problem(B * out[2] * out[3], O) or bn_layer_problem(bn))
+            return None if bad else out
 
-        y = conv_ok(x, self.conv1, self.bn1)
-        y = conv_ok(y, self.conv2, self.bn2) if y is not None else None
-        y = conv_ok(y, self.conv3, self.bn3) if y is not None else None
-        if y is None:
+        if train_tensors_problem(x, self.conv1.weight, None, self.conv1.in_channels):
             return False
-        r = x if self.downsample is None else conv_ok(x, self.downsample[0], self.downsample[1])
-        return r is not None and train_bn_ok(y, self.bn3, r)
+        y = r = tuple(x.shape)
+        for conv, bn in self._own_norm_layers()[:3]:
+            y = y and conv_bn(y, conv, bn)
+        r = r if self.downsample is None else conv_bn(r, *self.downsample)
+        return y is not None and r == y             # (bn3's residual, x or the downsample's output, has the output's shape)
 
     def _forward_own_norm(self, x):
         """the unfolded block in training mode on the own kernels: conv1 -> BN + ReLU, conv2 (stride 1 or 2) -> BN + ReLU,

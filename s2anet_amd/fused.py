@@ -345,69 +345,67 @@ def drop_weight_caches(module):
     return module
 
 
+def train_shape_problem(ksize, stride, padding, dilation, groups, C, O, B, H, W):
+    """why the dense training kernels cannot run this C -> O convolution on a [B, C, H, W] input, or None.  Plain values, and the
+    ONE statement of these limits in Python: the conjunction of what the forward, the input gradient and the weight gradient
+    of either stride and the pack accept (tests/test_train_limits_cpu.py holds it against the library's own queries)."""
+    k, st, pd = tuple(ksize), tuple(stride), tuple(padding)
+    if not (((k == (3, 3) and pd == (1, 1)) or (k == (1, 1) and pd == (0, 0))) and st in ((1, 1), (2, 2)) and
+            tuple(dilation) == (1, 1) and groups == 1):
+        return "not 3x3 / pad 1 or 1x1 / pad 0 at stride 1 or 2, dilation 1, groups 1"
+    if C % 64 != 0 or O % 64 != 0 or (st == (2, 2) and k == (3, 3) and O % 128 != 0):
+        return "channel counts are no multiples of 64 (out_channels of 128 for 3x3 at stride 2)"
+    Ho, Wo = (H - 1) // st[0] + 1, (W - 1) // st[1] + 1
+    ok = (min(B, C, O, H, W) > 0 and H < 32000 and W < 32000 and B < (1 << 31) and C < (1 << 24) and O < (1 << 24) and
+          B * H * W * C * 2 < (1 << 31) and B * Ho * Wo * O * 2 < (1 << 31) and O * C * k[0] * k[1] * 4 < (1 << 31))
+    return None if ok else "empty, a map side of 32000 or more, or input, output or filter of 2^31 bytes or more"
+
+
+def train_tensors_problem(x, weight, bias, c_in, residual=None, c_out=None, stride=(1, 1)):
+    """what train_shape_problem cannot say, or None: x f16 channels-last 4-D, non-empty, on the GPU, c_in wide (x = None: an
+    activation the route itself produces, which is all that); weight f16 or f32 on the GPU, bias of its dtype or None; a
+    residual of the output's shape ([B, c_out, Ho, Wo] at `stride`), dtype and layout"""
+    CL = torch.channels_last
+    if x is not None and not (x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 and x.numel() > 0 and
+                              x.is_contiguous(memory_format=CL) and x.shape[1] == c_in):
+        return "x is not a non-empty f16 channels-last 4-D tensor of the layer's width on the GPU"
+    if weight.dtype not in (torch.float16, torch.float32) or not weight.is_cuda or (bias is not None and bias.dtype != weight.dtype):
+        return "the weight is not f16 or f32 on the GPU, or the bias has another dtype"
+    if residual is not None and not (
+            residual.is_cuda and residual.dtype == torch.float16 and residual.is_contiguous(memory_format=CL) and
+            tuple(residual.shape) == (x.shape[0], c_out, (x.shape[2] - 1) // stride[0] + 1, (x.shape[3] - 1) // stride[1] + 1)):
+        return "the residual has not the output's shape, dtype and layout"
+    return None
+
+
+def _train_problem(x, weight, bias, stride, padding, dilation, groups, residual=None, widths=None):
+    """the two checks on an [O,C,k,k] filter; widths: the (C, O) the kernels would see when not the filter's own (train_pad_widths)"""
+    O, C = weight.shape[:2]
+    return (train_tensors_problem(x, weight, bias, C, residual, O, tuple(stride)) or
+            train_shape_problem(weight.shape[2:], stride, padding, dilation, groups, *(widths or (C, O)), x.shape[0], *x.shape[2:]))
+
+
+def _train_conv_problem(x, conv, residual=None, widths=None):
+    return _train_problem(x, conv.weight, conv.bias, conv.stride, conv.padding, conv.dilation, conv.groups, residual, widths)
+
+
 def train_conv_ok(x, conv, residual=None):
-    """limits of the own training route (FusedConvFunction), and nothing but limits: f16 channels-last activations on the
-    GPU, stride 1, 3x3 / pad 1 or 1x1 / pad 0, channel counts multiples of 64, f16 or f32 parameters, a residual of the
-    output's shape and layout, input and output under 2^31 bytes.  The speed heuristics of own_conv_ok play no part:
-    a layer on this route is bit-reproducible whatever its size."""
-    return _train_conv_limits(x, conv, residual, conv.in_channels, conv.out_channels)
-
-
-def _train_conv_limits(x, conv, residual, C, O):
-    """train_conv_ok at the channel counts C -> O the kernels would see (the layer's own, or its padded ones: train_pad_widths)"""
-    return _train_limits(x, conv.weight, conv.bias, conv.kernel_size, conv.stride, conv.padding, conv.dilation, conv.groups,
-                         residual, conv.in_channels, conv.out_channels, C, O)
+    """limits of the own training route (FusedConvFunction), and nothing but limits: stride 1, what train_tensors_problem asks
+    of x, the parameters and the residual, and what train_shape_problem asks of the geometry, the widths and the sizes.  The
+    speed heuristics of own_conv_ok play no part: a layer on this route is bit-reproducible whatever its size."""
+    return tuple(conv.stride) == (1, 1) and _train_conv_problem(x, conv, residual) is None
 
 
 def train_filter_ok(x, weight, bias, stride, padding, dilation, groups):
     """train_conv_ok for a bare [O,C,k,k] filter (ORConv2d's expansion, which is no module's parameter)"""
-    return weight.dim() == 4 and _train_limits(x, weight, bias, weight.shape[2:], stride, padding, dilation, groups, None,
-                                               weight.shape[1], weight.shape[0], weight.shape[1], weight.shape[0])
-
-
-def _train_limits(x, w, b, kernel_size, stride, padding, dilation, groups, residual, c_in, c_out, C, O):
-    """c_in -> c_out: the layer's own widths (what x and the residual must have); C -> O: the widths the kernels would see"""
-    if not (x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 and x.numel() > 0 and
-            x.is_contiguous(memory_format=torch.channels_last)):
-        return False
-    k, pd = tuple(kernel_size), tuple(padding)
-    if not (tuple(dilation) == (1, 1) and groups == 1 and tuple(stride) == (1, 1) and
-            ((k == (3, 3) and pd == (1, 1)) or (k == (1, 1) and pd == (0, 0))) and
-            C % 64 == 0 and O % 64 == 0 and x.shape[1] == c_in):
-        return False
-    if w.dtype not in (torch.float16, torch.float32) or not w.is_cuda or (b is not None and b.dtype != w.dtype):
-        return False
-    B, _, H, W = x.shape
-    if residual is not None and not (residual.is_cuda and residual.dtype == torch.float16 and
-                                     tuple(residual.shape) == (B, c_out, H, W) and
-                                     residual.is_contiguous(memory_format=torch.channels_last)):
-        return False
-    return B * H * W * C * 2 < (1 << 31) and B * H * W * O * 2 < (1 << 31)
+    return weight.dim() == 4 and tuple(stride) == (1, 1) and _train_problem(x, weight, bias, stride, padding, dilation, groups) is None
 
 
 def train_conv_strided_ok(x, conv, residual=None):
-    """limits of the own training route of the stride-2 layers (FusedConvS2Function), and nothing but limits: stride (2, 2),
-    3x3 / pad 1 with O % 128 == 0 (the forward kernel's limit) or 1x1 / pad 0, dilation 1, groups 1, C and O multiples of 64,
-    f16 channels-last x on the GPU, f16 or f32 weight with a bias of the same dtype or none, a residual of the OUTPUT's
-    shape and layout, input and output under 2^31 bytes.  No speed heuristic plays a part, as in train_conv_ok."""
-    if not (x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 and x.numel() > 0 and
-            x.is_contiguous(memory_format=torch.channels_last)):
-        return False
-    k, pd, C, O = tuple(conv.kernel_size), tuple(conv.padding), conv.in_channels, conv.out_channels
-    if not (tuple(conv.dilation) == (1, 1) and conv.groups == 1 and tuple(conv.stride) == (2, 2) and
-            ((k == (3, 3) and pd == (1, 1) and O % 128 == 0) or (k == (1, 1) and pd == (0, 0))) and
-            C % 64 == 0 and O % 64 == 0 and x.shape[1] == C):
-        return False
-    w, b = conv.weight, conv.bias
-    if w.dtype not in (torch.float16, torch.float32) or not w.is_cuda or (b is not None and b.dtype != w.dtype):
-        return False
-    B, _, H, W = x.shape
-    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    if residual is not None and not (residual.is_cuda and residual.dtype == torch.float16 and
-                                     tuple(residual.shape) == (B, O, Ho, Wo) and
-                                     residual.is_contiguous(memory_format=torch.channels_last)):
-        return False
-    return B * H * W * C * 2 < (1 << 31) and B * Ho * Wo * O * 2 < (1 << 31) and O * C * k[0] * k[1] * 4 < (1 << 31)
+    """limits of the own training route of the stride-2 layers (FusedConvS2Function), and nothing but limits: stride (2, 2) and
+    the two checks of train_conv_ok, in which a 3x3 then needs O % 128 == 0 (the forward kernel's limit) and the residual has
+    the OUTPUT's shape.  No speed heuristic plays a part, as in train_conv_ok."""
+    return tuple(conv.stride) == (2, 2) and _train_conv_problem(x, conv, residual) is None
 
 
 def train_pad_widths(x, conv):
@@ -416,9 +414,8 @@ def train_pad_widths(x, conv):
     inputs (odm_cls_ls[0] behind the orientation pooling: C' = 64) under O % 64 == 0 filters; None otherwise"""
     C, O = conv.in_channels, conv.out_channels
     Cp, Op = (64 if C == 32 else C), (64 if 0 < O < 64 else O)
-    if (Cp, Op) == (C, O) or not _train_conv_limits(x, conv, None, Cp, Op):
-        return None
-    return Cp, Op
+    ok = (Cp, Op) != (C, O) and tuple(conv.stride) == (1, 1) and _train_conv_problem(x, conv, None, (Cp, Op)) is None
+    return (Cp, Op) if ok else None
 
 
 def padded_train_conv(x, weight, bias, relu, Cp, Op):
@@ -463,19 +460,25 @@ def train_kernels(module, enabled=True, strided=False, entry=False):
     return n
 
 
+def _train_pack(weight, need_x, device):
+    """s2a_conv_pack_weight_train -> (the filter in forward order, in input-gradient order when x wants a gradient, else None)"""
+    O, C, k, _ = weight.shape
+    w = weight.detach()
+    w = w if w.is_contiguous() else w.contiguous()            # (a channels-last 3x3 filter: one stock copy)
+    fwd = torch.empty((w.numel(),), dtype=torch.float16, device=device)
+    dgrad = torch.empty_like(fwd) if need_x else None
+    with torch.cuda.device(device):
+        _lib.check(_lib.lib().s2a_conv_pack_weight_train(_lib.ptr(w), _lib.dtype_code(w), O, C, k, _lib.ptr(fwd), _lib.ptr(dgrad),
+                                                         _lib.stream_ptr(device)))
+    return fwd, dgrad
+
+
 def _train_forward(ctx, x, weight, bias, residual, relu, stride):
     """the forward both training Functions share: pack (forward order and, when x wants a gradient, input-gradient order),
     s2a_conv_nhwc_f16 at `stride` with bias and residual fused, the stock in-place ReLU; saves what the backward needs"""
     O, C, k, _ = weight.shape
-    L = _lib.lib()
     need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-    w = weight.detach()
-    w = w if w.is_contiguous() else w.contiguous()            # (a channels-last 3x3 filter: one stock copy)
-    fwd = torch.empty((w.numel(),), dtype=torch.float16, device=x.device)
-    dgrad = torch.empty_like(fwd) if need_x else None
-    with torch.cuda.device(x.device):
-        _lib.check(L.s2a_conv_pack_weight_train(_lib.ptr(w), _lib.dtype_code(w), O, C, k, _lib.ptr(fwd), _lib.ptr(dgrad),
-                                                _lib.stream_ptr(x.device)))
+    fwd, dgrad = _train_pack(weight, need_x, x.device)
     # the launch's fused ReLU is inference's (NaN -> 0, include/s2anet_hip.h): training runs it with relu = 0 and
     # applies the stock in-place ReLU, which keeps a NaN; the finite entries get the same bits either way
     out = conv_f16(x, fwd, None if bias is None else bias.detach(), O, k, stride, False, residual)
@@ -509,6 +512,17 @@ def _train_prep(ctx, grad_out, out, positions):
     return g, gb
 
 
+def _train_wgrad(x, g, geom):
+    """the stride-1 weight gradient (s2a_conv_backward_weight_f16) of ctx.geom, in the weight's dtype; under g's device"""
+    (B, C, H, W), O, k, wdtype, _ = geom
+    L, dev = _lib.lib(), g.device
+    gw = torch.empty((O, C, k, k), dtype=wdtype, device=dev)
+    ws = torch.empty((L.s2a_conv_backward_weight_f16_workspace_bytes(B, C, H, W, O, k),), dtype=torch.uint8, device=dev)
+    _lib.check(L.s2a_conv_backward_weight_f16(_lib.ptr(x), _lib.ptr(g), _lib.ptr(gw), _lib.dtype_code(gw), B, C, H, W, O, k,
+                                              _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+    return gw
+
+
 class FusedConvFunction(torch.autograd.Function):
     """relu?(conv(x) + bias (+ residual)) with its backward on the own kernels.  x f16 channels-last; weight / bias f16
     or f32 (masters: rounded to f16 by the pack, gradients straight from the f32 sums); stride 1, 3x3 / pad 1 or 1x1.
@@ -526,18 +540,12 @@ class FusedConvFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         x, out, dgrad = ctx.saved_tensors
-        (B, C, H, W), O, k, wdtype, _ = ctx.geom
+        (B, C, H, W), _, k = ctx.geom[:3]
         need_x, need_w, _, need_r = ctx.needs_input_grad[:4]
-        L, dev = _lib.lib(), grad_out.device
-        with torch.cuda.device(dev):
+        with torch.cuda.device(grad_out.device):
             g, gb = _train_prep(ctx, grad_out, out, B * H * W)
             gx = conv_f16(g, dgrad, None, C, k, 1, False) if need_x else None
-            gw = None
-            if need_w:
-                gw = torch.empty((O, C, k, k), dtype=wdtype, device=dev)
-                ws = torch.empty((L.s2a_conv_backward_weight_f16_workspace_bytes(B, C, H, W, O, k),), dtype=torch.uint8, device=dev)
-                _lib.check(L.s2a_conv_backward_weight_f16(_lib.ptr(x), _lib.ptr(g), _lib.ptr(gw), _lib.dtype_code(gw), B, C, H, W,
-                                                          O, k, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+            gw = _train_wgrad(x, g, ctx.geom) if need_w else None
         return gx, gw, gb, (g if need_r else None), None
 
 
@@ -581,6 +589,8 @@ class FusedConvS2Function(torch.autograd.Function):
 def train_up2_ok(x, conv, coarse):
     """limits of FusedConvUp2Function, and nothing but limits: a 1x1 lateral inside train_conv_ok, a coarser level of
     exactly half the size in f16 channels-last with the lateral's output width, and something that requires grad"""
+    # (s2a_conv1x1_add_up2_f16 has no pointer-free query to hold its own limits against: what stands here beyond train_conv_ok
+    # is read off its entry point, not pinned by tests/test_train_limits_cpu.py)
     return (train_conv_ok(x, conv) and tuple(conv.kernel_size) == (1, 1) and coarse.is_cuda and coarse.dtype == torch.float16 and
             coarse.dim() == 4 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and
             tuple(coarse.shape) == (x.shape[0], conv.out_channels, x.shape[2] // 2, x.shape[3] // 2) and
@@ -597,16 +607,9 @@ class FusedConvUp2Function(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, coarse):
-        O, C = weight.shape[:2]
-        L = _lib.lib()
+        O = weight.shape[0]
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        w = weight.detach()
-        w = w if w.is_contiguous() else w.contiguous()
-        fwd = torch.empty((w.numel(),), dtype=torch.float16, device=x.device)
-        dgrad = torch.empty_like(fwd) if need_x else None
-        with torch.cuda.device(x.device):
-            _lib.check(L.s2a_conv_pack_weight_train(_lib.ptr(w), _lib.dtype_code(w), O, C, 1, _lib.ptr(fwd), _lib.ptr(dgrad),
-                                                    _lib.stream_ptr(x.device)))
+        fwd, dgrad = _train_pack(weight, need_x, x.device)          # (a 1x1 filter: train_up2_ok)
         b = None if bias is None else bias.detach().to(torch.float16).contiguous()
         out = conv1x1_add_up2(x, fwd, b, coarse.detach(), O)
         ctx.save_for_backward(x if need_w else None, dgrad)
@@ -617,7 +620,7 @@ class FusedConvUp2Function(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         x, dgrad = ctx.saved_tensors
-        (B, C, H, W), O, _, wdtype, _ = ctx.geom
+        (B, C, H, W), O = ctx.geom[:2]
         need_x, need_w, _, need_c = ctx.needs_input_grad[:4]
         L, dev = _lib.lib(), grad_out.device
         gx = gw = gc = None
@@ -626,10 +629,7 @@ class FusedConvUp2Function(torch.autograd.Function):
             if need_x:
                 gx = conv_f16(g, dgrad, None, C, 1, 1, False)
             if need_w:
-                gw = torch.empty((O, C, 1, 1), dtype=wdtype, device=dev)
-                ws = torch.empty((L.s2a_conv_backward_weight_f16_workspace_bytes(B, C, H, W, O, 1),), dtype=torch.uint8, device=dev)
-                _lib.check(L.s2a_conv_backward_weight_f16(_lib.ptr(x), _lib.ptr(g), _lib.ptr(gw), _lib.dtype_code(gw), B, C, H, W,
-                                                          O, 1, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+                gw = _train_wgrad(x, g, ctx.geom)
             if need_c:
                 gc = torch.empty((B, O, H // 2, W // 2), dtype=torch.float16, device=dev, memory_format=torch.channels_last)
                 _lib.check(L.s2a_sum_pool2x2_f16(_lib.ptr(g), _lib.ptr(gc), B, H, W, O, _lib.stream_ptr(dev)))

@@ -11,6 +11,35 @@ from . import _lib
 _CL = torch.channels_last
 
 
+_BN_WIDTH, _BN_BYTES = "the channel count is not bn.num_features or no multiple of 64", "2^31 bytes or more"
+
+
+def bn_shape_problem(P, C):
+    """why the kernels cannot take a [P, C] problem (P = B H W positions of C channels), or None: bn::plan_ok of csrc/bn_plan.hpp
+    on the Python side, and its one statement there (tests/test_train_limits_cpu.py holds it against s2a_bn_slices)"""
+    if not (C > 0 and C % 64 == 0):
+        return _BN_WIDTH
+    if P < 2:
+        return "fewer than 2 values per channel"
+    return None if C < (1 << 24) and P < (1 << 31) and P * C * 2 < (1 << 31) else _BN_BYTES
+
+
+def bn_layer_problem(bn, need_cuda=True):
+    """why an nn.BatchNorm2d's own state keeps it off the kernels, whatever it is fed, or None"""
+    if not (bn.affine and bn.track_running_stats) or bn.weight is None or bn.running_mean is None:
+        return "the layer is not affine with running statistics"
+    if not isinstance(bn.momentum, float):
+        return "momentum is not a float"
+    w, b, rm, rv = bn.weight, bn.bias, bn.running_mean, bn.running_var
+    if w.dtype not in (torch.float16, torch.float32) or b.dtype != w.dtype:
+        return "weight and bias are not both float16 or both float32"
+    if rm.dtype != rv.dtype or rm.dtype not in (torch.float32, w.dtype):
+        return "running statistics are neither float32 nor the parameters' dtype"
+    if need_cuda and not (w.is_cuda and b.is_cuda and rm.is_cuda and rv.is_cuda):
+        return "the layer is not on the GPU"
+    return None
+
+
 def _bn_problem(x, bn, residual=None, need_cuda=True):
     """why batch_norm_train cannot take (x, bn, residual), or None.  Limits only, no speed heuristic.  need_cuda=False leaves
     the device out (the other limits can then be read off CPU tensors)"""
@@ -23,34 +52,20 @@ def _bn_problem(x, bn, residual=None, need_cuda=True):
     if x.dim() != 4 or x.numel() == 0 or not x.is_contiguous(memory_format=_CL):
         return "x is not a channels-last 4-D tensor"
     B, C, H, W = x.shape
-    if C != bn.num_features or C % 64 != 0:
-        return "the channel count is not bn.num_features or no multiple of 64"
-    if B * H * W < 2:
-        return "fewer than 2 values per channel"
-    if not (bn.affine and bn.track_running_stats) or bn.weight is None or bn.running_mean is None:
-        return "the layer is not affine with running statistics"
-    if not isinstance(bn.momentum, float):
-        return "momentum is not a float"
-    w, b, rm, rv = bn.weight, bn.bias, bn.running_mean, bn.running_var
-    if w.dtype not in (torch.float16, torch.float32) or b.dtype != w.dtype:
-        return "weight and bias are not both float16 or both float32"
-    if rm.dtype != rv.dtype or rm.dtype not in (torch.float32, w.dtype):
-        return "running statistics are neither float32 nor the parameters' dtype"
-    if need_cuda and not (w.is_cuda and b.is_cuda and rm.is_cuda and rv.is_cuda):
-        return "the layer is not on the GPU"
+    shape = _BN_WIDTH if C != bn.num_features else bn_shape_problem(B * H * W, C)
+    if shape not in (None, _BN_BYTES):
+        return shape
     if residual is not None and not ((residual.is_cuda or not need_cuda) and residual.dtype == torch.float16 and
                                      tuple(residual.shape) == tuple(x.shape) and residual.is_contiguous(memory_format=_CL)):
-        return "the residual has not the output's shape, dtype and layout"
-    if x.numel() * 2 >= (1 << 31):
-        return "2^31 bytes or more"
-    return None
+        shape = "the residual has not the output's shape, dtype and layout"
+    return bn_layer_problem(bn, need_cuda) or shape         # (the layer's own state, then the residual, the size limits last)
 
 
 def train_bn_ok(x, bn, residual=None):
     """limits of the own training route of a BatchNorm2d (BatchNormTrainFunction), and nothing but limits: a CUDA f16
     channels-last 4-D x with C == bn.num_features, C % 64 == 0 and at least 2 values per channel; an affine layer with running
     statistics and a float momentum; weight and bias of one dtype, f16 or f32; running statistics in f32 or that dtype; a
-    residual of the output's shape and layout; tensors under 2^31 bytes"""
+    residual of the output's shape and layout; tensors under 2^31 bytes, C under 2^24 (bn_shape_problem)"""
     return _bn_problem(x, bn, residual) is None
 
 

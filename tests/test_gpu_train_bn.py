@@ -246,6 +246,23 @@ def test_own_route_never_reaches_the_library(kind, monkeypatch):
         blk(x.float())                                       # the control: an f32 input is outside and takes the stock route
 
 
+@pytest.mark.parametrize("kind", ["layer1_0", "s2_down"])
+def test_own_norm_ok_creates_no_tensor(kind):
+    """the block's question is answered on shapes and parameters: not one byte is allocated, not even for a moment"""
+    import s2anet_amd as S
+    blk, inp = make_block(kind)
+    S.train_batchnorm(blk)
+    x = randn((2, inp, 24, 24), F16, 3, cl=True, grad=True)
+    blk.__dict__.pop("_own_norm_cache", None)
+    torch.cuda.synchronize()
+    before = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    with torch.enable_grad():
+        ok = blk._own_norm_ok(x)
+    assert ok is True
+    assert torch.cuda.memory_allocated() == before and torch.cuda.max_memory_allocated() == before
+
+
 def _step(blk, x, cot):
     for p in blk.parameters():
         p.grad = None

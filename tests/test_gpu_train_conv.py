@@ -30,13 +30,17 @@ CASES = {  # name: (k, B, C, O, H, W, relu, residual, bias)
     "1x1_relu_res_3x512x128_7x9": (1, 3, 512, 128, 7, 9, True, True, True),
     "1x1_nobias_2x64x320_5x5": (1, 2, 64, 320, 5, 5, False, False, False),
 }
+SIDE_LIMIT = {  # a map side of 32000: outside the library's limits and outside train_shape_problem; x is 4 and 8 MB
+    "1x1_1x64x64_32000x1": (1, 1, 64, 64, 32000, 1, False, False, True),
+    "3x3_1x64x128_2x32000": (3, 1, 64, 128, 2, 32000, False, False, True),
+}
 PATTERNS = {"ALL": "xwbr", "X": "x", "PAR": "wb", "BIAS": "b", "RES": "r"}
 TENSORS = {"x": "x", "w": "weight", "b": "bias", "r": "residual"}
 
 
 def make(case, master, seed=11):
     from s2anet_amd.fused import FusedConv2d
-    k, B, C, O, H, W, relu, res, bias = CASES[case]
+    k, B, C, O, H, W, relu, res, bias = CASES.get(case) or SIDE_LIMIT[case]
     torch.manual_seed(seed)
     m = FusedConv2d(C, O, k, 1, k // 2, bias=bias, relu=relu).to(DEV, F32 if master else F16)
     if bias:
@@ -92,13 +96,14 @@ def rel(a, ref):
     return float((a.to(F64) - ref.to(F64)).norm() / ref.to(F64).norm())
 
 
-def verify(tag, m, x, r, cot, master, patterns=tuple(PATTERNS)):
+def verify(tag, m, x, r, cot, master, patterns=tuple(PATTERNS), autocast_on=False):
+    """autocast_on: the run with the switches on is under autocast too (a layer whose route then is the stock one)"""
     bad = []
     for pattern in patterns:
         what = PATTERNS[pattern]
         if not any((c == "x") or (c == "w") or (c == "b" and m.bias is not None) or (c == "r" and r is not None) for c in what):
             continue                                        # (BIAS without a bias, RES without a residual)
-        prod = run(m, x, r, cot, pattern, True)
+        prod = run(m, x, r, cot, pattern, True, autocast=autocast_on)
         stock = run(m, x, r, cot, pattern, False, autocast=master)
         mask = prod["out"] > 0
         ref, pre = reference(m, x, r, cot, mask)
@@ -136,16 +141,34 @@ def test_accuracy_every_pattern(case, master):
     verify("%s/%s" % (case, "f32" if master else "f16"), m, x, r, cot, master)
 
 
+def _boom(*a, **kw):
+    raise AssertionError("a route was reached that this step must not take")
+
+
 @pytest.mark.parametrize("case", ["3x3_relu_res_2x64x64_9x21", "1x1_nobias_2x64x320_5x5"])
 def test_route_eligible_never_reaches_the_library(case, monkeypatch):
     from s2anet_amd import fused
     m, x, r, cot = make(case, True)
-
-    def boom(*a, **kw):
-        raise AssertionError("F.conv2d reached on the own training route")
-    monkeypatch.setattr(fused.F, "conv2d", boom)
+    monkeypatch.setattr(fused.F, "conv2d", _boom)
     got = run(m, x, r, cot, "ALL", True)
     assert got["x"] is not None and got["weight"] is not None
+
+
+@pytest.mark.parametrize("case", list(SIDE_LIMIT))
+def test_behind_the_side_limit_the_stock_route_runs(case, monkeypatch):
+    """a map side of 32000 is outside the library's limits: the predicate says so, and the grad-enabled step takes the stock
+    route (under autocast, as every stock step of f32 masters) instead of raising from the C entry point; output and
+    gradients meet the bound of the accuracy cases.  The stock route is F.conv2d whatever serves it: here torch's own GEMM
+    convolution, because MIOpen builds its solvers for a 2 x 32000 map on first use, 7 to 17 s of host time for 1 ms of work"""
+    import s2anet_amd as S
+    from s2anet_amd import fused
+    monkeypatch.setattr(torch.backends.cudnn, "enabled", False)
+    m, x, r, cot = make(case, True)
+    S.train_kernels(m, True, strided=True)
+    assert not S.train_conv_ok(x, m, r) and not S.train_conv_strided_ok(x, m, r)
+    monkeypatch.setattr(fused.FusedConvFunction, "apply", _boom)
+    monkeypatch.setattr(fused.FusedConvS2Function, "apply", _boom)
+    verify(case, m, x, r, cot, True, patterns=("ALL",), autocast_on=True)
 
 
 @pytest.mark.parametrize("which", ["stride2", "narrow15", "nchw"])
