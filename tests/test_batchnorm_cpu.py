@@ -24,10 +24,13 @@ from conftest import ROOT
 F64 = torch.float64
 
 # the GPU grid: name -> (B, C, H, W).  The first six are the issue's; the last is there because at 64 channels the plan has
-# 256 slices, more than the 180 tiles of 40 x 72: "more tiles than slices" needs 2 x 96 x 96 (576 tiles)
+# 256 slices, more than the 180 tiles of 40 x 72: "more tiles than slices" needs 2 x 96 x 96 (576 tiles).  The eighth is the
+# only one whose lanes own five rows or more, so that k_bn_stats runs its four-rows-in-flight loop: 3 x 117 x 117 = 41067 rows,
+# 192 per slice, the last used slice ragged (tests/test_bn_geometry_cpu.py asserts this from the plan)
 SHAPES = {
     "smallest": (2, 64, 1, 1), "ragged": (3, 320, 7, 9), "wide_rows": (2, 2048, 4, 4), "tiles_40x72": (2, 64, 40, 72),
     "offset": (2, 64, 16, 16), "constant_channel": (2, 64, 5, 5), "more_tiles_than_slices": (2, 64, 96, 96),
+    "unrolled_ragged": (3, 64, 117, 117),
 }
 # the trunk's batch-8 shapes of scripts/bench_train_bn.py, covered by the plan walk as well
 BENCH_SHAPES = [(8, 64, 256, 256), (8, 256, 256, 256), (8, 128, 128, 128), (8, 512, 128, 128), (8, 1024, 64, 64), (8, 2048, 32, 32)]

@@ -7,8 +7,9 @@ the SAME nn.BatchNorm2d with the stock add and ReLU on the same f16 channels-las
 values.  The ReLU mask is judged as in tests/test_gpu_train_conv.py: the float64 backward takes production's mask (out > 0),
 and wherever the float64 pre-activation exceeds BAND[F16] * rms in magnitude the mask must agree with its sign.
 
-Shapes: tests/test_batchnorm_cpu.py:SHAPES -- the issue's six and one more for "more tiles than slices" (at 64 channels the
-plan has 256 slices, and 40 x 72 only 180 tiles).
+Shapes: tests/test_batchnorm_cpu.py:SHAPES -- the issue's six, one more for "more tiles than slices" (at 64 channels the
+plan has 256 slices, and 40 x 72 only 180 tiles), and 3 x 117 x 117, the one whose lanes own more than four rows (the
+unrolled loop of k_bn_stats; per channel and per element that walk is held by tests/test_gpu_bn_geometry.py).
 
 The capture test runs two blocks: layer1[0] as the trunk has it (64 -> 64 -> 256, stride 1, with downsample) and a stride-2
 block with downsample at 64 -> 128 -> 512.  A 64 -> 64 -> 256 block at stride 2 is outside train_conv_strided_ok (the 3x3 / s2
